@@ -2,10 +2,14 @@
 """bench.py -- depth-frames/s integrated (640x480 -> 512^3 TSDF @ 2 cm) on MI355X, with the HBM roofline fraction of the dominant
 kernel, the CPU restatement timed beside it and the measured deviation from the reference-literal semantics.
 
-    python bench.py --gpus N --steps K --warmup W [--config 2|1|3|4]
+    python bench.py --gpus N --steps K --warmup W [--config 2|1|3|4] [--full] [--dump-outputs DIR]
 
 A "step" is one pass of the hot path over one synthetic depth frame (BASELINE.json configs[1], the default --config 2): frames and
-poses are generated up front and are resident in HBM before the timed region starts.  --gpus N > 1 launches one process per GPU (this
+poses are generated up front and are resident in HBM before the timed region starts.  A plain run sets up, warms up, times exactly K
+steps and prints the line; --full adds everything else the line used to carry (repeated bursts, per-kernel and roofline figures, the
+steady and host-input legs, the CPU baselines, the exactness checks, the other configurations, the one-GPU merge).  --dump-outputs DIR
+writes the map the timed steps built as DIR/*.npy (float32), so that two builds can be compared output for output.
+--gpus N > 1 launches one process per GPU (this
 script re-executes itself under torch.distributed.run when it is not already running under it): each rank integrates its own stream
 into its own submap -- the path shards by submap with no data-path collective, so scaling is weak -- and after
 the timed region the ranks merge their submaps into one global map with ONE exchange over RCCL (configs[4]; reported as `merge`).
@@ -29,6 +33,30 @@ C2 = dict(map_scale=[10.24, 10.24], voxel_scale=0.02, num_voxel_per_blk_axis=16,
 HBM_PEAK_GBS = 8000.0      # MI355X HBM3E spec peak (MI355X_MICROARCH.md); ~6300 GB/s achievable copy
 WORKLOAD = ("BASELINE configs[1]: single 640x480 u16 depth stream (sphere room r=3 m, 1 deg/frame) -> DenseTSDF 512^3 / 2 cm, "
             "recast_step 2, max_ray 5 m; one stream+submap per GPU")
+# the stream turns 1 degree per frame: a plain run makes one turn of distinct frames at most and goes round it again, so that its set-up
+# does not grow with --steps (--full keeps every frame distinct: its legs index the stream by frame number)
+POOL_FRAMES = 360
+DUMP_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, export, seed=0):
+    """What the timed path hands its caller -- the submap as export_submap() returns it -- as float32 DIR/<name>.npy, voxels in index order.  Above
+    DUMP_BYTES a fixed share of the voxels is kept, chosen by a seeded hash of the voxel index, so that two builds keep the same voxels."""
+    idx = np.asarray(export["indices"]).astype(np.int64)
+    key = ((idx[:, 0] + 32768) << 32) | ((idx[:, 1] + 32768) << 16) | (idx[:, 2] + 32768)
+    cols = {"indices": idx.astype(np.float32), "TSDF": np.asarray(export["TSDF"]).astype(np.float32),
+            "W_TSDF": np.asarray(export["W_TSDF"]).astype(np.float32), "occupy": np.asarray(export["occupy"]).astype(np.float32)}
+    total = sum(v.nbytes for v in cols.values())
+    keep = np.ones(key.shape[0], bool)
+    if total > DUMP_BYTES:
+        h = (key.astype(np.uint64) ^ np.uint64(seed)) * np.uint64(0x9E3779B97F4A7C15)
+        h ^= h >> np.uint64(31)
+        keep = (h % np.uint64(1 << 20)) < np.uint64(int((1 << 20) * 0.9 * DUMP_BYTES / total))
+    order = np.argsort(key[keep], kind="stable")
+    os.makedirs(out_dir, exist_ok=True)
+    for name, v in cols.items():
+        np.save(os.path.join(out_dir, name + ".npy"), v[keep][order])
+    return {"dir": out_dir, "voxels": int(key.shape[0]), "voxels_written": int(order.shape[0]), "sampled": bool(total > DUMP_BYTES)}
 
 
 # ---- CPU legs (the oracle is only the measured baseline / the checker here, never the product path) --------------------------------
@@ -387,9 +415,18 @@ def main():
     ap.add_argument("--as-rank", type=int, default=None, metavar="R", help="dry run of the multi-rank branch on ONE GPU: behave as rank R of --of N (stream offset, "
                     "submap id, pose table of N submaps, merge leg) without any collective; the line is marked dry_run and its value is this rank's alone")
     ap.add_argument("--of", type=int, default=8, metavar="N", help="world size of the --as-rank dry run")
-    ap.add_argument("--bursts", type=int, default=7, help="timed regions of K steps; `value` is their median (1 = the single region of the contract)")
-    ap.add_argument("--steady", type=int, default=300, help="frames of the steady-state leg behind the contract region (0 = off)")
+    ap.add_argument("--bursts", type=int, default=None, help="timed regions of K steps; `value` is their median (default 1, the single region of the contract; "
+                    "7 with --full)")
+    ap.add_argument("--steady", type=int, default=300, help="--full: frames of the steady-state leg behind the contract region (0 = off)")
+    ap.add_argument("--full", action="store_true", help="everything beyond the headline: repeated bursts, per-kernel / roofline figures, steady and host-input "
+                    "legs, CPU baselines, exactness checks, the other configurations, the one-GPU merge")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the map the timed steps built (export_submap, float32, voxels in index order) "
+                    "as DIR/<name>.npy")
     args = ap.parse_args()
+    if args.bursts is None:
+        args.bursts = 7 if args.full else 1
+    if args.dump_outputs and args.config != 2:
+        raise SystemExit("--dump-outputs writes the headline path's map: --config 2 only")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(relaunch(args))
@@ -445,11 +482,13 @@ def main():
     # ---- synthetic stream: each rank starts 45 degrees further round the room ----
     nframes = args.warmup + args.steps
     from taichislam_amd import distributed as D
-    nsteady = args.steady if (args.steady > 0 and (rank == 0 or dry)) else 0
+    nsteady = args.steady if (args.full and args.steady > 0 and (rank == 0 or dry)) else 0
     ngen = nframes + max(0, nsteady - args.steps)            # the steady-state leg goes over the timed frames again and on along the stream
-    host = list(syn.sphere_room_stream(ngen, start_deg=D.stream_start_deg(rank)))
+    npool = ngen if args.full else min(ngen, POOL_FRAMES)
+    host = list(syn.sphere_room_stream(npool, start_deg=D.stream_start_deg(rank)))
     depth_dev = torch.from_numpy(np.stack([d for _, _, d in host]).view(np.int16)).cuda(dev)   # resident in HBM
     poses = [(np.ascontiguousarray(R), np.ascontiguousarray(T)) for R, T, _ in host]
+    poses = [poses[f % npool] for f in range(ngen)]
 
     nsub = max(8, world) + 1
     m = DenseTSDF(**C2, device=dev, max_submap_num=nsub, max_bricks=32768)
@@ -462,7 +501,7 @@ def main():
         if not k.startswith("fuse_"):
             m.set_option(k, int(v))
 
-    frames_dev = [depth_dev[f] for f in range(ngen)]        # one [480, 640] view per frame, made before the timed region
+    frames_dev = [depth_dev[f % npool] for f in range(ngen)]        # one [480, 640] view per frame, made before the timed region
 
     def step(f):
         R, T = poses[f]
@@ -471,8 +510,8 @@ def main():
     for f in range(args.warmup):
         step(f)
     m.sync()
-    # timed region: only the dominant kernel is bracketed by HIP events (one pair per batch of its launches)
-    if not os.environ.get("TSL_BENCH_NOPROF"):      # developer A/B: what the event pair around every phase-B launch costs
+    # timed region: with --full, the dominant kernel is bracketed by HIP events (one pair per batch of its launches) for its roofline figure
+    if args.full and not os.environ.get("TSL_BENCH_NOPROF"):      # developer A/B: what the event pair around every phase-B launch costs
         m.enable_profiling(True, only=[_lib.K_INTEGRATE])
 
     def barrier():
@@ -507,25 +546,27 @@ def main():
     bursts = [timed_burst() for _ in range(max(1, args.bursts))]
     order = sorted(range(len(bursts)), key=lambda i: bursts[i][0])
     dt, dt_rank = bursts[order[(len(bursts) - 1) // 2]]
-    dom_ms, dom_n = m.kernel_time(_lib.K_INTEGRATE)
     stats = m.last_frame_stats()
-    # second, untimed pass over some of the same frames with every kernel bracketed: the per-kernel breakdown
-    m.enable_profiling(True)
-    for f in range(args.warmup, min(nframes, args.warmup + 60)):
-        step(f)
-    m.sync()
+    dumped = dump_outputs(args.dump_outputs, m.export_submap()) if args.dump_outputs and (rank == 0 or dry) else None
     kern = {}
-    for kid, name in _lib.KERNEL_NAMES.items():
-        ms, n = m.kernel_time(kid)
-        if n:
-            kern[name] = {"avg_us": 1000.0 * ms / n, "launches": n}
-    m.enable_profiling(False)
-    if dom_n:
-        kern["integrate"] = {"avg_us": 1000.0 * dom_ms / dom_n, "launches": dom_n, "measured_in": "timed region"}
+    if args.full:
+        dom_ms, dom_n = m.kernel_time(_lib.K_INTEGRATE)
+        # second, untimed pass over some of the same frames with every kernel bracketed: the per-kernel breakdown
+        m.enable_profiling(True)
+        for f in range(args.warmup, min(nframes, args.warmup + 60)):
+            step(f)
+        m.sync()
+        for kid, name in _lib.KERNEL_NAMES.items():
+            ms, n = m.kernel_time(kid)
+            if n:
+                kern[name] = {"avg_us": 1000.0 * ms / n, "launches": n}
+        m.enable_profiling(False)
+        if dom_n:
+            kern["integrate"] = {"avg_us": 1000.0 * dom_ms / dom_n, "launches": dom_n, "measured_in": "timed region"}
 
     # ---- the same frames handed over as HOST buffers, as the reference API does (H2D copy inside the timed loop; never `value`) ----
     host_rates = None
-    if rank == 0:
+    if args.full and rank == 0:
         nsrc = min(args.steps, 200)                        # distinct host images
         nh = max(nsrc, 300)                                # calls: a stream, like value_steady, not a burst (the images are handed over again and again)
         pinned = torch.from_numpy(np.stack([host[args.warmup + i][2] for i in range(nsrc)]).view(np.int16)).pin_memory().numpy().view(np.uint16)
@@ -615,7 +656,7 @@ def main():
         merge_box["done"] = True
 
     merge_timed_out = False
-    if distributed or args.merge or dry or not args.no_cpu_baseline:          # (the default N = 1 line carries configs[4]'s one-GPU form as well)
+    if distributed or args.merge or dry or (args.full and not args.no_cpu_baseline):          # (the --full N = 1 line carries configs[4]'s one-GPU form as well)
         import threading
         th = threading.Thread(target=merge_leg, daemon=True)
         th.start()
@@ -676,10 +717,14 @@ def main():
             "value_host_input": host_rates,
             "host_numa": host_numa,
         }
+        if not args.full:                       # a plain run measures the headline alone
+            del out["config"]["kernels_us"], out["roofline"], out["value_steady"], out["value_host_input"]
+        if dumped:
+            out["outputs"] = dumped
         if dry:
             out["dry_run"] = {"as_rank": rank, "of": world, "note": "single-process dry run of the multi-rank branch: this rank's stream offset, submap id and pose table, "
                               "merge leg without a communicator; `value` is this rank's rate alone"}
-        if not args.no_cpu_baseline and world == 1:              # the CPU legs: rank 0 at N = 1 only (the other ranks of a multi-GPU run would wait at the barrier)
+        if args.full and not args.no_cpu_baseline and world == 1:              # the CPU legs: rank 0 at N = 1 only (the other ranks of a multi-GPU run would wait at the barrier)
             sample = [(R, T, d) for R, T, d in host[: max(8, min(len(host), 200))]]
             one, allc, omap, n_done = cpu_baselines(sample)
             out["cpu_baseline"] = one
@@ -723,16 +768,17 @@ def main():
             for k in ks:
                 d = d.get(k) if isinstance(d, dict) else None
             return d
-        cf = out.get("configs") or {}
-        out["summary"] = {"value_burst_median": fps, "burst_runs": out["burst_runs"]["frames_per_s"], "value_steady": _v(steady, "value"),
-                          "value_sequential": {"value": _v(out, "value_sequential", "value"), "value_steady": _v(out, "value_sequential", "value_steady"),
-                                               "bit_exact": _v(out, "value_sequential", "bit_exact_with_oracle_FAITHFUL")},
-                          "value_host_input": {"pageable": _v(host_rates, "pageable"), "pinned": _v(host_rates, "pinned")},
-                          "c1_meshes_per_s": _v(cf, "c1_marching_cubes_128", "value"), "c3_octomap_frames_per_s": _v(cf, "c3_octomap_1024", "value"), "c3_host_images_frames_per_s": _v(cf, "c3_octomap_1024", "detail", "host_input_frames_per_s"),
-                          "c4_tsdf_esdf_mesh_frames_per_s": _v(cf, "c4_tsdf_esdf_mesh", "value"), "c4_esdf_ms_per_update": _v(cf, "c4_tsdf_esdf_mesh", "detail", "esdf_ms_per_update"),
-                          "c4_wavefront": {"frames_per_s": _v(cf, "c4_esdf_wavefront", "value"), "esdf_ms": _v(cf, "c4_esdf_wavefront", "esdf_ms_per_update"), "voxel_writes": _v(cf, "c4_esdf_wavefront", "esdf_voxel_pushes_per_update")},
-                          "c5_merge_one_gpu_ms": _v(merge, "ms"), "roofline_frac": _v(roof, "frac"), "cpu_baseline_frames_per_s": _v(out, "cpu_baseline", "value"),
-                          "parity_ok": out.get("parity_ok")}
+        if args.full:
+            cf = out.get("configs") or {}
+            out["summary"] = {"value_burst_median": fps, "burst_runs": out["burst_runs"]["frames_per_s"], "value_steady": _v(steady, "value"),
+                              "value_sequential": {"value": _v(out, "value_sequential", "value"), "value_steady": _v(out, "value_sequential", "value_steady"),
+                                                   "bit_exact": _v(out, "value_sequential", "bit_exact_with_oracle_FAITHFUL")},
+                              "value_host_input": {"pageable": _v(host_rates, "pageable"), "pinned": _v(host_rates, "pinned")},
+                              "c1_meshes_per_s": _v(cf, "c1_marching_cubes_128", "value"), "c3_octomap_frames_per_s": _v(cf, "c3_octomap_1024", "value"), "c3_host_images_frames_per_s": _v(cf, "c3_octomap_1024", "detail", "host_input_frames_per_s"),
+                              "c4_tsdf_esdf_mesh_frames_per_s": _v(cf, "c4_tsdf_esdf_mesh", "value"), "c4_esdf_ms_per_update": _v(cf, "c4_tsdf_esdf_mesh", "detail", "esdf_ms_per_update"),
+                              "c4_wavefront": {"frames_per_s": _v(cf, "c4_esdf_wavefront", "value"), "esdf_ms": _v(cf, "c4_esdf_wavefront", "esdf_ms_per_update"), "voxel_writes": _v(cf, "c4_esdf_wavefront", "esdf_voxel_pushes_per_update")},
+                              "c5_merge_one_gpu_ms": _v(merge, "ms"), "roofline_frac": _v(roof, "frac"), "cpu_baseline_frames_per_s": _v(out, "cpu_baseline", "value"),
+                              "parity_ok": out.get("parity_ok")}
         emit(out)
     if merge_timed_out:
         sys.stderr.write("bench.py: merge leg timed out; leaving without further collectives\n"); real_stdout.flush()

@@ -463,7 +463,7 @@ def test_the_reference_session_on_the_hip_maps(hip_lib):
         assert np.percentile(d, 50) <= 0.02 * 0.08 and np.percentile(d, 99) <= 0.6 * 0.08, np.percentile(d, [50, 99])
 
 
-@pytest.mark.skipif(not os.path.exists("/root/reference/taichi_slam/mapping/submap_mapping.py"), reason="needs the reference tree (dev box)")
+@pytest.mark.skipif(not os.path.exists(__import__("test_reference_callers").REF), reason="needs the reference's submap_mapping.py (tree or oracle/_ref/)")
 def test_the_reference_orchestration_itself_on_the_oracle_maps():
     """The third side of the triangle, where the reference tree exists: the REFERENCE's submap_mapping.py (loaded by path, unmodified) driving the oracle-backed
     maps ends with the same two global maps as the reference's orchestration on the reference's maps (the vector) and as the package's orchestration on the

@@ -4,13 +4,15 @@
 tree, unmodified, into a stand-in `taichi_slam.mapping` package whose `DenseTSDF` / `Octomap` / `BaseMap` are supplied by the test.
 Nothing of the reference is vendored: where the tree is absent (the GPU box) these tests skip.
 
-  * CPU (here): the reference class and `taichislam_amd.mapping.SubmapMapping` are driven through the same scenario on a recording
-    stand-in for the map classes; the two call traces into the map classes, the wire buffers and the bookkeeping must be identical.
-    That is what makes the package's own class a faithful substitute where the reference file cannot be loaded.
+  * CPU: `taichislam_amd.mapping.SubmapMapping` is driven through a scenario on a recording stand-in for the map classes; its call trace
+    into the map classes, the wire buffers and the bookkeeping must be identical to the reference class's in the same scenario, recorded in
+    tests/golden/ref_callers_scenario.json (tools/gen_ref_api_golden.py).  That is what makes the package's own class a faithful substitute
+    where the reference file cannot be loaded.
   * GPU (a box that has both a GPU and the reference tree): the reference class runs on the real HIP-backed shims and its global
     map must equal the CPU oracle's fusion of the same submaps bit for bit."""
 import importlib.util
 import io
+import json
 import os
 import sys
 import types
@@ -26,6 +28,7 @@ _REF_TREE = "/root/reference/taichi_slam/mapping/submap_mapping.py"
 _REF_CACHE = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "oracle", "_ref", "submap_mapping.py")
 REF = _REF_TREE if os.path.exists(_REF_TREE) else _REF_CACHE
 needs_ref = pytest.mark.skipif(not os.path.exists(REF), reason="neither the reference tree nor oracle/_ref/submap_mapping.py (python __graft_entry__.py) is present")
+GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "ref_callers_scenario.json")
 
 
 def load_reference_submap_mapping(DenseTSDF, Octomap, BaseMap):
@@ -185,17 +188,32 @@ def _scenario(SM, tsdf_cls, octo_cls, kind):
     return trace, sent_maps, sent_traj, book
 
 
-@needs_ref
+def canonical(x):
+    """A scenario's result in JSON form (tuples as lists, numpy scalars as Python numbers, dicts as sorted [key, value] pairs), as stored in
+    tests/golden/ref_callers_scenario.json"""
+    if isinstance(x, (list, tuple)):
+        return [canonical(v) for v in x]
+    if isinstance(x, dict):
+        return {"__dict__": sorted(([canonical(k), canonical(v)] for k, v in x.items()), key=repr)}
+    if isinstance(x, np.generic):
+        return x.item()
+    return x
+
+
+def reference_scenario(kind):
+    """The reference class through _scenario, in canonical form: what tools/gen_ref_api_golden.py records"""
+    return canonical(_scenario(load_reference_submap_mapping(RecTSDF, RecOcto, RecBase), RecTSDF, RecOcto, kind))
+
+
 @pytest.mark.parametrize("kind", ["tsdf", "octo"])
 def test_package_submap_mapping_makes_the_same_calls_as_the_reference(kind):
     from taichislam_amd.mapping import submap_mapping as mine
-    Ref = load_reference_submap_mapping(RecTSDF, RecOcto, RecBase)
+    a = json.load(open(GOLD))[kind]
     # the package class picks its defaults by `issubclass(submap_type, Octomap)`: give it the recording classes under its own names
     old = (mine.DenseTSDF, mine.Octomap)
     mine.DenseTSDF, mine.Octomap = RecTSDF, RecOcto
     try:
-        a = _scenario(Ref, RecTSDF, RecOcto, kind)
-        b = _scenario(mine.SubmapMapping, RecTSDF, RecOcto, kind)
+        b = json.loads(json.dumps(canonical(_scenario(mine.SubmapMapping, RecTSDF, RecOcto, kind))))
     finally:
         mine.DenseTSDF, mine.Octomap = old
     assert len(a[0]) > 40

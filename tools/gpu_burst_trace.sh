@@ -1,7 +1,8 @@
 #!/bin/bash
+R=$(cd "$(dirname "$0")/.." && pwd)
 # kernel timeline of the driver's 20-frame burst (bench.py --gpus 1 --steps 20 --warmup 5): the launches between the warm-up's last apply and the end
 O=$GRAFT_REPO_ROOT/gpurun_out/burst; mkdir -p $O; export TMPDIR=/tmp
-cd /tmp && timeout 300 rocprofv3 --kernel-trace --output-format csv -d $O/kt -o p -- python $GRAFT_REPO_ROOT/bench.py --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline --steady 0 "$@" > $O/bench.json 2>/dev/null
+cd /tmp && timeout 300 rocprofv3 --kernel-trace --output-format csv -d $O/kt -o p -- python $R/bench.py --full --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline --steady 0 "$@" > $O/bench.json 2>/dev/null
 tail -1 $O/bench.json | python $GRAFT_REPO_ROOT/tools/bench_brief.py burst
 f=$(find $O/kt -name "*kernel_trace.csv" | head -1)
 python - "$f" << 'PY'

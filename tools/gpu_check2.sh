@@ -1,6 +1,7 @@
 #!/bin/bash
+R=$(cd "$(dirname "$0")/.." && pwd)
 cd $GRAFT_REPO_ROOT; export TMPDIR=/tmp; O=$GRAFT_REPO_ROOT/gpurun_out/ks; mkdir -p $O
-cd /tmp && timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/t -o p -- python $GRAFT_REPO_ROOT/bench.py --steps 200 --warmup 20 --no-cpu-baseline > $O/ks.log 2>&1
+cd /tmp && timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/t -o p -- python $R/bench.py --full --steps 200 --warmup 20 --no-cpu-baseline > $O/ks.log 2>&1
 f=$(find $O/t -name "*kernel_stats.csv" | head -1); python - "$(find $O/t -name '*kernel_trace.csv' | head -1)" << 'PY'
 import csv, sys
 rows = sorted(csv.DictReader(open(sys.argv[1])), key=lambda r: int(r["Start_Timestamp"]))

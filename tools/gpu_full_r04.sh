@@ -1,7 +1,7 @@
 cd $GRAFT_REPO_ROOT; export TMPDIR=/tmp; O=$GRAFT_REPO_ROOT/gpurun_out/full; mkdir -p $O
 timeout 900 python -m pytest tests -x -q -m gpu 2>&1 | tail -8 | tee $O/tests.log
 timeout 200 python tools/seq_probe.py --frames 400 --warmup 40 2>&1 | grep -v "^TSDF\|^Export" | tee $O/probe_steady.log
-timeout 600 python bench.py --gpus 1 --steps 20 --warmup 5 > $O/bench_driver_cmd.json 2> $O/bench_driver_cmd.err; tail -c 600 $O/bench_driver_cmd.err
+timeout 600 python bench.py --full --gpus 1 --steps 20 --warmup 5 > $O/bench_driver_cmd.json 2> $O/bench_driver_cmd.err; tail -c 600 $O/bench_driver_cmd.err
 python - $O/bench_driver_cmd.json <<'PY'
 import json, sys
 j = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])

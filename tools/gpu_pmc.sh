@@ -1,11 +1,12 @@
 #!/bin/bash
+R=$(cd "$(dirname "$0")/.." && pwd)
 # rocprofv3 PMC passes over a short bench run.  usage: gpu_pmc.sh tag "CTR1 CTR2 ..." ["CTR..." ...]  (one pass per quoted group)
 TAG=$1; shift
 O=$GRAFT_REPO_ROOT/gpurun_out; mkdir -p $O; export TMPDIR=/tmp
 n=0
 for grp in "$@"; do
   n=$((n+1))
-  cd /tmp && timeout 600 rocprofv3 --pmc $grp --kernel-trace --output-format csv -d $O/pmc_${TAG}_$n -o p -- python $GRAFT_REPO_ROOT/bench.py --steps 20 --warmup 5 --no-cpu-baseline $BENCH_ARGS > $O/pmc_${TAG}_$n.log 2>&1
+  cd /tmp && timeout 600 rocprofv3 --pmc $grp --kernel-trace --output-format csv -d $O/pmc_${TAG}_$n -o p -- python $R/bench.py --full --steps 20 --warmup 5 --no-cpu-baseline $BENCH_ARGS > $O/pmc_${TAG}_$n.log 2>&1
   f=$(find $O/pmc_${TAG}_$n -name "*counter_collection.csv" | head -1)
   echo "== pass $n: $grp -> $f"
   python - "$f" << 'PY'

@@ -11,9 +11,9 @@ stats() {  # tag, command...
 }
 pmc() {  # tag, counters, bench args...
   tag=$1; ctr=$2; shift; shift
-  cd /tmp && timeout 600 rocprofv3 --pmc $ctr --kernel-trace --output-format csv -d $O/pmc_$tag -o p -- python $R/bench.py --steps 20 --warmup 5 --no-cpu-baseline "$@" > $O/pmc_$tag.log 2>&1
+  cd /tmp && timeout 600 rocprofv3 --pmc $ctr --kernel-trace --output-format csv -d $O/pmc_$tag -o p -- python $R/bench.py --full --steps 20 --warmup 5 --no-cpu-baseline "$@" > $O/pmc_$tag.log 2>&1
   f=$(find $O/pmc_$tag -name "*counter_collection.csv" | head -1)
-  echo "== $tag: rocprofv3 --pmc $ctr --kernel-trace -- python bench.py --steps 20 --warmup 5 --no-cpu-baseline $*" >> $O/pmc_summary.txt
+  echo "== $tag: rocprofv3 --pmc $ctr --kernel-trace -- python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline $*" >> $O/pmc_summary.txt
   python - "$f" >> $O/pmc_summary.txt << 'PY'
 import csv, sys, collections
 agg = collections.defaultdict(lambda: collections.defaultdict(list))
@@ -26,8 +26,8 @@ PY
   rm -rf $O/pmc_$tag
 }
 : > $O/pmc_summary.txt
-cd $R && timeout 600 python bench.py > $O/bench_default.json 2> $O/bench_default.err
-stats bench python $R/bench.py --steps 100 --warmup 10 --no-cpu-baseline
+cd $R && timeout 600 python bench.py --full > $O/bench_default.json 2> $O/bench_default.err
+stats bench python $R/bench.py --full --steps 100 --warmup 10 --no-cpu-baseline
 for cfg in ""; do
   t=$(echo "c$cfg" | tr -d ' =-')
   pmc fetch_$t "FETCH_SIZE" $cfg
@@ -39,7 +39,7 @@ pmc tcc "TCC_HIT_sum TCC_MISS_sum"
 stats c1 python $R/bench.py --config 1 --steps 50 --warmup 5
 stats c3 python $R/bench.py --config 3 --steps 100 --warmup 10
 stats c4 python $R/bench.py --config 4 --steps 60 --warmup 10
-stats merge python $R/bench.py --steps 20 --warmup 5 --no-cpu-baseline --merge
+stats merge python $R/bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --merge
 cd $R
 for c in 1 3 4; do timeout 300 python bench.py --config $c --steps 100 --warmup 10 2>/dev/null | tail -1 > $O/bench_c$c.json; done
 ls $O; cat $O/pmc_summary.txt | grep -i "integrate_bricks\|=="

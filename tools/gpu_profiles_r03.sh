@@ -29,11 +29,11 @@ PY
   rm -rf $O/pmc_$tag
 }
 : > $O/pmc_summary.txt
-cd $R && timeout 600 python bench.py > $O/bench_default.json 2> $O/bench_default.err
-cd $R && timeout 300 python bench.py --gpus 1 --steps 20 --warmup 5 > $O/bench_driver_cmd.json 2> $O/bench_driver_cmd.err
-cd $R && timeout 300 python bench.py --as-rank 3 --of 8 --steps 20 --warmup 5 --no-cpu-baseline > $O/bench_dry_rank3of8.json 2> /dev/null
-B20="python $R/bench.py --steps 20 --warmup 5 --no-cpu-baseline --steady 0"
-stats bench python $R/bench.py --steps 100 --warmup 10 --no-cpu-baseline --steady 0
+cd $R && timeout 600 python bench.py --full > $O/bench_default.json 2> $O/bench_default.err
+cd $R && timeout 300 python bench.py --full --gpus 1 --steps 20 --warmup 5 > $O/bench_driver_cmd.json 2> $O/bench_driver_cmd.err
+cd $R && timeout 300 python bench.py --full --as-rank 3 --of 8 --steps 20 --warmup 5 --no-cpu-baseline > $O/bench_dry_rank3of8.json 2> /dev/null
+B20="python $R/bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --steady 0"
+stats bench python $R/bench.py --full --steps 100 --warmup 10 --no-cpu-baseline --steady 0
 stats bench_driver_cmd $B20
 pmc fetch "FETCH_SIZE" $B20
 pmc write "WRITE_SIZE" $B20
@@ -45,9 +45,9 @@ for c in 1 3 4; do
   pmc fetch_c$c "FETCH_SIZE" python $R/bench.py --config $c --steps 20 --warmup 5 --no-cpu-baseline
   pmc write_c$c "WRITE_SIZE" python $R/bench.py --config $c --steps 20 --warmup 5 --no-cpu-baseline
 done
-stats merge python $R/bench.py --steps 20 --warmup 5 --no-cpu-baseline --steady 0 --merge
-pmc fetch_merge "FETCH_SIZE" python $R/bench.py --steps 20 --warmup 5 --no-cpu-baseline --steady 0 --merge
-pmc write_merge "WRITE_SIZE" python $R/bench.py --steps 20 --warmup 5 --no-cpu-baseline --steady 0 --merge
+stats merge python $R/bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --steady 0 --merge
+pmc fetch_merge "FETCH_SIZE" python $R/bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --steady 0 --merge
+pmc write_merge "WRITE_SIZE" python $R/bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --steady 0 --merge
 cd $R
 for c in 1 3 4; do timeout 300 python bench.py --config $c --steps 100 --warmup 10 2>/dev/null | tail -1 > $O/bench_c$c.json; done
 timeout 600 python tools/parity_report.py 12 $O/parity_vs_faithful.json > $O/parity_summary.json 2>/dev/null

@@ -8,9 +8,9 @@ stats() {  # tag, command...
   f=$(find $O/ks_$tag -name "*kernel_stats.csv" | head -1); [ -n "$f" ] && cp "$f" $O/${tag}_kernel_stats.csv
   rm -rf $O/ks_$tag; cd $R
 }
-timeout 200 python bench.py --gpus 1 --steps 20 --warmup 5 > $O/bench_driver_cmd.json 2> $O/bench_driver_cmd.err
-stats bench_driver_cmd python $R/bench.py --steps 20 --warmup 5 --no-cpu-baseline --steady 0
-stats bench python $R/bench.py --steps 100 --warmup 10 --no-cpu-baseline --steady 0
-timeout 240 python bench.py > $O/bench_default.json 2> $O/bench_default.err
+timeout 200 python bench.py --full --gpus 1 --steps 20 --warmup 5 > $O/bench_driver_cmd.json 2> $O/bench_driver_cmd.err
+stats bench_driver_cmd python $R/bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --steady 0
+stats bench python $R/bench.py --full --steps 100 --warmup 10 --no-cpu-baseline --steady 0
+timeout 240 python bench.py --full > $O/bench_default.json 2> $O/bench_default.err
 for f in $O/bench_default.json $O/bench_driver_cmd.json; do tail -1 $f | python tools/bench_brief.py $(basename $f); done
 grep -h k_integrate_batch $O/bench_kernel_stats.csv $O/bench_driver_cmd_kernel_stats.csv | cut -c1-60,200-

@@ -31,10 +31,10 @@ PY
 : > $O/pmc_summary.txt
 # (first pass without the CPU legs: make_r05_profiles.py only needs the frame statistics of the driver's command; the full lines are printed at the end,
 #  once the counters of THESE sources exist)
-cd $R && timeout 300 python bench.py --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline > $O/bench_driver_cmd.json 2> $O/bench_driver_cmd.err
-cd $R && timeout 300 python bench.py --as-rank 3 --of 8 --steps 20 --warmup 5 --no-cpu-baseline > $O/bench_dry_rank3of8.json 2> /dev/null
-B20="python $R/bench.py --steps 20 --warmup 5 --no-cpu-baseline --steady 0"
-stats bench python $R/bench.py --steps 100 --warmup 10 --no-cpu-baseline --steady 0
+cd $R && timeout 300 python bench.py --full --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline > $O/bench_driver_cmd.json 2> $O/bench_driver_cmd.err
+cd $R && timeout 300 python bench.py --full --as-rank 3 --of 8 --steps 20 --warmup 5 --no-cpu-baseline > $O/bench_dry_rank3of8.json 2> /dev/null
+B20="python $R/bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --steady 0"
+stats bench python $R/bench.py --full --steps 100 --warmup 10 --no-cpu-baseline --steady 0
 stats bench_driver_cmd $B20
 pmc fetch "FETCH_SIZE" $B20
 pmc write "WRITE_SIZE" $B20
@@ -46,9 +46,9 @@ for c in 1 3 4; do
   pmc fetch_c$c "FETCH_SIZE" python $R/bench.py --config $c --steps 20 --warmup 5 --no-cpu-baseline
   pmc write_c$c "WRITE_SIZE" python $R/bench.py --config $c --steps 20 --warmup 5 --no-cpu-baseline
 done
-stats merge python $R/bench.py --steps 20 --warmup 5 --no-cpu-baseline --steady 0 --merge
-pmc fetch_merge "FETCH_SIZE" python $R/bench.py --steps 20 --warmup 5 --no-cpu-baseline --steady 0 --merge
-pmc write_merge "WRITE_SIZE" python $R/bench.py --steps 20 --warmup 5 --no-cpu-baseline --steady 0 --merge
+stats merge python $R/bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --steady 0 --merge
+pmc fetch_merge "FETCH_SIZE" python $R/bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --steady 0 --merge
+pmc write_merge "WRITE_SIZE" python $R/bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --steady 0 --merge
 # the sequential semantics (rounds 4-5): kernel table of a 400-frame stream, SQ counters of the replay and the grouping kernels
 SEQ="python $R/tools/seq_probe.py --frames 400 --warmup 40"
 stats seq $SEQ
@@ -67,7 +67,7 @@ PY
 # the counters are in: reduce them here too (profiles/r05_traffic.json of THIS copy, stamped with these sources' hash) and print the bench lines
 # again, now with `roofline.traffic` from counters collected on the same sources a minute ago
 cd $R && python tools/make_r05_profiles.py > /dev/null 2>&1
-cd $R && timeout 600 python bench.py > $O/bench_default.json 2> $O/bench_default.err
-cd $R && timeout 300 python bench.py --gpus 1 --steps 20 --warmup 5 > $O/bench_driver_cmd.json 2> $O/bench_driver_cmd.err
+cd $R && timeout 600 python bench.py --full > $O/bench_default.json 2> $O/bench_default.err
+cd $R && timeout 300 python bench.py --full --gpus 1 --steps 20 --warmup 5 > $O/bench_driver_cmd.json 2> $O/bench_driver_cmd.err
 for c in 1 3 4; do timeout 300 python bench.py --config $c --steps 100 --warmup 10 2>/dev/null | tail -1 > $O/bench_c$c.json; done
 ls $O; grep -c . $O/pmc_summary.txt

@@ -31,10 +31,10 @@ PY
 : > $O/pmc_summary.txt
 # (first pass without the CPU legs: make_r06_profiles.py only needs the frame statistics of the driver's command; the full lines are printed at the end,
 #  once the counters of THESE sources exist)
-cd $R && timeout 300 python bench.py --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline > $O/bench_driver_cmd.json 2> $O/bench_driver_cmd.err
-cd $R && timeout 300 python bench.py --as-rank 3 --of 8 --steps 20 --warmup 5 --no-cpu-baseline > $O/bench_dry_rank3of8.json 2> /dev/null
-B20="python $R/bench.py --steps 20 --warmup 5 --no-cpu-baseline --steady 0"
-stats bench python $R/bench.py --steps 100 --warmup 10 --no-cpu-baseline --steady 0
+cd $R && timeout 300 python bench.py --full --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline > $O/bench_driver_cmd.json 2> $O/bench_driver_cmd.err
+cd $R && timeout 300 python bench.py --full --as-rank 3 --of 8 --steps 20 --warmup 5 --no-cpu-baseline > $O/bench_dry_rank3of8.json 2> /dev/null
+B20="python $R/bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --steady 0"
+stats bench python $R/bench.py --full --steps 100 --warmup 10 --no-cpu-baseline --steady 0
 stats bench_driver_cmd $B20
 pmc fetch "FETCH_SIZE" $B20
 pmc write "WRITE_SIZE" $B20
@@ -50,9 +50,9 @@ done
 TSL_C4_OPTS="esdf_mode=1" stats c4w python $R/bench.py --config 4 --steps 60 --warmup 10 --no-cpu-baseline
 TSL_C4_OPTS="esdf_mode=1" pmc fetch_c4w "FETCH_SIZE" python $R/bench.py --config 4 --steps 20 --warmup 5 --no-cpu-baseline
 TSL_C4_OPTS="esdf_mode=1" pmc write_c4w "WRITE_SIZE" python $R/bench.py --config 4 --steps 20 --warmup 5 --no-cpu-baseline
-stats merge python $R/bench.py --steps 20 --warmup 5 --no-cpu-baseline --steady 0 --merge
-pmc fetch_merge "FETCH_SIZE" python $R/bench.py --steps 20 --warmup 5 --no-cpu-baseline --steady 0 --merge
-pmc write_merge "WRITE_SIZE" python $R/bench.py --steps 20 --warmup 5 --no-cpu-baseline --steady 0 --merge
+stats merge python $R/bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --steady 0 --merge
+pmc fetch_merge "FETCH_SIZE" python $R/bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --steady 0 --merge
+pmc write_merge "WRITE_SIZE" python $R/bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --steady 0 --merge
 # the sequential semantics (rounds 4-5): kernel table of a 400-frame stream, SQ counters of the replay and the grouping kernels
 SEQ="python $R/tools/seq_probe.py --frames 400 --warmup 40"
 stats seq $SEQ
@@ -71,8 +71,8 @@ PY
 # the counters are in: reduce them here too (profiles/r06_traffic.json of THIS copy, stamped with these sources' hash) and print the bench lines
 # again, now with `roofline.traffic` from counters collected on the same sources a minute ago
 cd $R && python tools/make_r06_profiles.py > /dev/null 2>&1
-cd $R && timeout 600 python bench.py > $O/bench_default.json 2> $O/bench_default.err
-cd $R && timeout 300 python bench.py --gpus 1 --steps 20 --warmup 5 > $O/bench_driver_cmd.json 2> $O/bench_driver_cmd.err
+cd $R && timeout 600 python bench.py --full > $O/bench_default.json 2> $O/bench_default.err
+cd $R && timeout 300 python bench.py --full --gpus 1 --steps 20 --warmup 5 > $O/bench_driver_cmd.json 2> $O/bench_driver_cmd.err
 for c in 1 3 4; do timeout 300 python bench.py --config $c --steps 100 --warmup 10 2>/dev/null | tail -1 > $O/bench_c$c.json; done
 TSL_C4_OPTS="esdf_mode=1" timeout 300 python bench.py --config 4 --steps 100 --warmup 10 --no-cpu-baseline 2>/dev/null | tail -1 > $O/bench_c4_wavefront.json
 timeout 300 python bench.py --config 3 --steps 1000 --warmup 50 --no-cpu-baseline 2>/dev/null | tail -1 > $O/bench_c3_1000.json

@@ -1,8 +1,9 @@
 #!/bin/bash
+R=$(cd "$(dirname "$0")/.." && pwd)
 # steady-state kernel timeline of the pipelined bench: gpu_steady.sh "opt=v opt=v" [tag]   (rocprofv3 --kernel-trace, middle of the timed region)
 cd $GRAFT_REPO_ROOT; export TMPDIR=/tmp; O=$GRAFT_REPO_ROOT/gpurun_out/steady; mkdir -p $O
 args=""; for kv in $1; do args="$args --opt $kv"; done
-cd /tmp && timeout 300 rocprofv3 --kernel-trace --output-format csv -d $O/t -o p -- python $GRAFT_REPO_ROOT/bench.py --steps 400 --warmup 40 --no-cpu-baseline $args > $O/run.log 2>&1
+cd /tmp && timeout 300 rocprofv3 --kernel-trace --output-format csv -d $O/t -o p -- python $R/bench.py --full --steps 400 --warmup 40 --no-cpu-baseline $args > $O/run.log 2>&1
 python - "$(find $O/t -name '*kernel_trace.csv' | head -1)" "$1" << 'PY'
 import csv, sys, collections
 rows = sorted(csv.DictReader(open(sys.argv[1])), key=lambda r: int(r["Start_Timestamp"]))

@@ -1,7 +1,7 @@
 #!/bin/bash
 # kernel timeline of a short bench run (the driver's command line): what the 20 timed frames actually wait for
 O=$GRAFT_REPO_ROOT/gpurun_out/tl; mkdir -p $O; export TMPDIR=/tmp; R=$GRAFT_REPO_ROOT
-cd /tmp && timeout 300 rocprofv3 --kernel-trace --output-format csv -d $O/t -o p -- python $R/bench.py --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline > $O/run.log 2>&1
+cd /tmp && timeout 300 rocprofv3 --kernel-trace --output-format csv -d $O/t -o p -- python $R/bench.py --full --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline > $O/run.log 2>&1
 python - "$(find $O/t -name '*kernel_trace.csv' | head -1)" << 'PY'
 import csv, sys
 rows = sorted(csv.DictReader(open(sys.argv[1])), key=lambda r: int(r["Start_Timestamp"]))

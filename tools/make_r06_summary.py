@@ -10,7 +10,7 @@ def stats(f):
 
 ks = stats("r06_bench_driver_cmd_kernel_stats.csv")
 L = ["# Round 6: kernels against their byte models (MI355X, HBM peak 8.0 TB/s)\n",
-     "Sources: `r06_bench_driver_cmd_kernel_stats.csv` (rocprofv3 --kernel-trace --stats over `python bench.py --steps 20 --warmup 5 --no-cpu-baseline --steady 0`: average launch),\n"
+     "Sources: `r06_bench_driver_cmd_kernel_stats.csv` (rocprofv3 --kernel-trace --stats over `python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --steady 0`: average launch),\n"
      "`r06_traffic.json` (separate `--pmc FETCH_SIZE` / `WRITE_SIZE` passes over the same command, `(2 x FETCH_SIZE + WRITE_SIZE) x 1024`), `r06_c*_kernel_stats.csv`, `r06_merge_kernel_stats.csv`.\n"
      "Kernel sources hash `%s` (`taichislam_amd.build.source_hash()`).  Made by `tools/make_r06_summary.py`.\n" % t["lib_source_hash"],
      "| kernel | launches | avg us | frames per launch | algorithmic MB per launch | counted HBM MB per launch | traffic / model | achieved GB/s (algorithmic) | of 8 TB/s |",
