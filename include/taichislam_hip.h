@@ -257,6 +257,23 @@ int  tsl_esdf_export_dev(tsl_tsdf* m, int64_t cap, void** idx_dev, void** val_de
 int  tsl_esdf_slice(tsl_tsdf* m, float z, int32_t* n);
 int  tsl_esdf_read_slice(tsl_tsdf* m, float* xyz, float* val, int64_t n);
 int  tsl_esdf_slice_dev(tsl_tsdf* m, void** xyz_dev, void** val_dev, int32_t* n);
+/* batched ESDF point queries for planners (tsl_esdf_query.hip).  xyz f32 [n][3] in the frame of the submap the ESDF was last updated for
+ * (the frame of tsl_tsdf_query_points).  A voxel is KNOWN when it is in the volume, its brick is allocated and it is observed; its value is
+ * the one tsl_esdf_export reports, with gamma / max_dist of the last update.
+ *   mode 0: the nearest voxel (rnd_i(x / voxel), as tsl_tsdf_query_points); no gradient (grad must be NULL).
+ *   mode 1: trilinear over the 8 corners of the cell floor(x / voxel), all of which must be known; grad (nullable) f32 [n][3] = the
+ *           gradient of that interpolant (per metre), in the fixed f32 evaluation order DESIGN.md gives.
+ * status u8 [n]: 0 ok, 1 a needed voxel is unknown, 2 a needed voxel is outside the volume or a coordinate is not finite (2 wins over 1);
+ * for 1 and 2 dist = unknown_value and grad = 0.  | 0x80: the values come from an update that stopped before converging (only the device
+ * form can see one; the next call that waits repairs it).  Errors: mode not 0 / 1, grad with mode 0, a null buffer, no update since the
+ * map was created, reset or imported, or an active submap other than the one of the last update.  n = 0 does nothing.
+ * The host form waits for the updates in flight first (never sees a short one); the device form is ASYNCHRONOUS like
+ * tsl_tsdf_query_points_dev: launched on the handle's stream behind every queued frame and the latest update, after the work queued on
+ * `user_stream`, which then waits for the result. */
+int  tsl_esdf_query_points(tsl_tsdf* m, int mode, float unknown_value, const float* xyz, int64_t n,
+                           float* dist, float* grad, uint8_t* status);
+int  tsl_esdf_query_points_dev(tsl_tsdf* m, int mode, float unknown_value, const void* xyz_dev, int64_t n,
+                               void* dist_dev, void* grad_dev, void* status_dev, void* user_stream);
 
 /* backend knobs for A/B-ing kernel variants: name in
      "variant"  0|1: one global int64 atomic pair per ray step, 2 (default): brick-binned LDS accumulation

@@ -131,6 +131,8 @@ SIGNATURES = {
     "tsl_esdf_slice": (C.c_int, [vp, f32, pi32]),
     "tsl_esdf_read_slice": (C.c_int, [vp, vp, vp, i64]),
     "tsl_esdf_slice_dev": (C.c_int, [vp, C.POINTER(vp), C.POINTER(vp), pi32]),
+    "tsl_esdf_query_points": (C.c_int, [vp, C.c_int, f32, vp, i64, vp, vp, vp]),
+    "tsl_esdf_query_points_dev": (C.c_int, [vp, C.c_int, f32, vp, i64, vp, vp, vp, vp]),
     "tsl_tsdf_set_option": (C.c_int, [vp, C.c_char_p, C.c_int]),
     "tsl_tsdf_get_option": (C.c_int, [vp, C.c_char_p, C.POINTER(C.c_int)]),
     "tsl_tsdf_prof_enable": (C.c_int, [vp, C.c_int]),

@@ -1355,6 +1355,7 @@ static int esdf_enqueue(tsl_tsdf* m, float gamma, float max_dist, bool force_ful
     S.rounds = rounds;
     ++m->esdf_npend;
     m->esdf_gamma = gamma; m->esdf_maxd = max_dist; m->esdf_submap = s; m->esdf_valid = true;
+    m->esdf_query_ok = true; m->esdf_q_ctr = ctr; m->esdf_q_rounds = rounds;      // tsl_esdf_query.hip: read behind this update, flag it if it stopped early
     return TSL_OK;
 }
 

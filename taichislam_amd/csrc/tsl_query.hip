@@ -51,6 +51,28 @@ __global__ void __launch_bounds__(256) k_query_raycast(MapDev M, int s, float vs
     len[q] = l;
 }
 
+// ---- device-buffer forms: nothing is staged, nothing is waited for.  The queries are launched on the handle's stream -- behind every frame
+// queued so far -- after what `user_stream` (a hipStream_t, e.g. torch's current stream; NULL = the legacy default stream, which is what
+// torch uses unless told otherwise) has queued, and `user_stream` is made to wait for them: a planner that expands a node with 64-128
+// rays (topo_graph.py:444-507) pays two event operations and one launch, no host round trip.  (Also used by tsl_esdf_query.hip.)
+int order_before(tsl_tsdf* m, hipStream_t user, hipStream_t q)
+{
+    if (user == q) return TSL_OK;
+    if (!m->in_ev[0]) for (auto& e : m->in_ev) TSL_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+    hipEvent_t e = m->in_ev[m->in_ev_next]; m->in_ev_next = (m->in_ev_next + 1) % 8;
+    TSL_HIP(hipEventRecord(e, user));
+    TSL_HIP(hipStreamWaitEvent(q, e, 0));
+    return TSL_OK;
+}
+int order_after(tsl_tsdf* m, hipStream_t user, hipStream_t q)
+{
+    if (user == q) return TSL_OK;
+    hipEvent_t e = m->in_ev[m->in_ev_next]; m->in_ev_next = (m->in_ev_next + 1) % 8;
+    TSL_HIP(hipEventRecord(e, q));
+    TSL_HIP(hipStreamWaitEvent(user, e, 0));
+    return TSL_OK;
+}
+
 }  // namespace tsl
 
 using namespace tsl;
@@ -90,28 +112,6 @@ int tsl_tsdf_query_raycast(tsl_tsdf* m, const float* pos, const float* dir, floa
     TSL_HIP(hipMemcpy(hit, dhit, c, hipMemcpyDeviceToHost));
     TSL_HIP(hipMemcpy(end_xyz, dend, c * 12, hipMemcpyDeviceToHost));
     TSL_HIP(hipMemcpy(len, dlen, c * 4, hipMemcpyDeviceToHost));
-    return TSL_OK;
-}
-
-// ---- device-buffer forms: nothing is staged, nothing is waited for.  The queries are launched on the handle's stream -- behind every frame
-// queued so far -- after what `user_stream` (a hipStream_t, e.g. torch's current stream; NULL = the legacy default stream, which is what
-// torch uses unless told otherwise) has queued, and `user_stream` is made to wait for them: a planner that expands a node with 64-128
-// rays (topo_graph.py:444-507) pays two event operations and one launch, no host round trip.
-static int order_before(tsl_tsdf* m, hipStream_t user, hipStream_t q)
-{
-    if (user == q) return TSL_OK;
-    if (!m->in_ev[0]) for (auto& e : m->in_ev) TSL_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-    hipEvent_t e = m->in_ev[m->in_ev_next]; m->in_ev_next = (m->in_ev_next + 1) % 8;
-    TSL_HIP(hipEventRecord(e, user));
-    TSL_HIP(hipStreamWaitEvent(q, e, 0));
-    return TSL_OK;
-}
-static int order_after(tsl_tsdf* m, hipStream_t user, hipStream_t q)
-{
-    if (user == q) return TSL_OK;
-    hipEvent_t e = m->in_ev[m->in_ev_next]; m->in_ev_next = (m->in_ev_next + 1) % 8;
-    TSL_HIP(hipEventRecord(e, q));
-    TSL_HIP(hipStreamWaitEvent(user, e, 0));
     return TSL_OK;
 }
 

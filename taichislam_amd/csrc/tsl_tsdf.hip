@@ -1288,7 +1288,7 @@ int tsl_tsdf_reset(tsl_tsdf* m)
     const int pending = tsl_tsdf_sync(m);          // a capacity error of the discarded contents is still reported, after the reset
     if (pending && pending != TSL_ERR_CAPACITY) return pending;
     int used = 0; int rc = tsl_tsdf_bricks_in_use(m, &used); if (rc) return rc;
-    m->esdf_valid = false;
+    m->esdf_valid = false; m->esdf_query_ok = false;
     if (used > 0) hipLaunchKernelGGL(k_reset_bricks, dim3(used < 4096 ? used : 4096), dim3(256), 0, ms(m), m->M, used);
     TSL_HIP(hipMemsetAsync(m->M.pool_top, 0, sizeof(int), ms(m)));
     TSL_HIP(hipGetLastError());
@@ -1494,7 +1494,7 @@ int tsl_tsdf_import_sparse(tsl_tsdf* m, int sid, const int16_t* idx, const uint1
     TSL_REQUIRE(idx && t && w, "import_sparse: null arrays");
     TSL_REQUIRE(sid >= 0 && (m->cfg.is_global_map || sid < m->nsub), "import_sparse: submap id out of range");
     TSL_HIP(hipSetDevice(m->device));
-    m->esdf_valid = false;
+    m->esdf_valid = false; m->esdf_query_ok = false;
     const size_t c = (size_t)n;
     const size_t o_idx = 0, o_t = o_idx + c * 6, o_w = o_t + c * 2, o_occ = o_w + c * 2, o_col = ((o_occ + c + 15) / 16) * 16, total = o_col + c * 6 + 64;
     int rc = grow(&m->xbuf, &m->xbuf_bytes, total); if (rc) return rc;

@@ -266,6 +266,8 @@ struct tsl_tsdf {
     float* esdf; uint8_t *esdf_fl, *esdf_region, *esdf_par, *esdf_ok; int esdf_mode, esdf_grid; bool fuse_direct; long long esdf_orphans; int *esdf_list, *esdf_queue, *esdf_ctr, *esdf_inq, *esdf_nbr; uint32_t* esdf_note; int esdf_qcap;      // tsl_esdf.hip
     float *esdf_exp_xyz, *esdf_exp_val; int* esdf_exp_count; int esdf_exp_n;      // export_ESDF_xyz / export_ESDF / num_export_ESDF_particles (dense_esdf.py:498-509), allocated by the first slice
     bool esdf_valid, esdf_force_full; int esdf_submap; float esdf_gamma, esdf_maxd; tsl_esdf_stats esdf_stats;
+    bool esdf_query_ok; int* esdf_q_ctr; int esdf_q_rounds;      // tsl_esdf_query.hip: the ESDF array belongs to the map (cleared by reset / import, not by an esdf_mode switch);
+                                                                 // device counters and rounds of the latest update (its early-stop test)
     hipEvent_t esdf_gate, esdf_gate_ev; bool esdf_gate_set; unsigned esdf_gate_mask;      // recorded behind the collect kernel of the latest ESDF update: phase A of later frames waits for it
                                                                                            // -- on EVERY phase-A stream (mask: the streams that have waited since the update was queued)
     hipEvent_t esdf_in, esdf_read, esdf_last;      // option "esdf_overlap": the relaxation rounds of update n run beside the integration of frame n + 1.
@@ -306,6 +308,8 @@ int  launch_slab_apply(tsl_tsdf* m, const BatchDev& B, const FrameParams& P);
 int  launch_seq_group(tsl_tsdf* m, const BatchDev& B, const FrameParams* hp, int bi, hipStream_t st);      // tsl_sequential.hip, phase A tail: replay ranks of the rays, per-brick replay runs
 int  launch_seq_apply(tsl_tsdf* m, const BatchDev& B, const FrameParams& P, int bi);                       // tsl_sequential.hip, phase B of a batch: every voxel's runs applied in frame order
 void seq_release(tsl_tsdf* m);
+int  order_before(tsl_tsdf* m, hipStream_t user, hipStream_t q);         // tsl_query.hip: device-buffer queries run on the handle's stream after `user`'s work ...
+int  order_after(tsl_tsdf* m, hipStream_t user, hipStream_t q);          // ... and `user` waits for them
 int  seq_prepare(tsl_tsdf* m);
 int  selftest_seqdiv(unsigned long long* bad_dev);
 int  seq_verify_report(tsl_tsdf* m, int* out, int cap);

@@ -598,6 +598,43 @@ class DenseTSDF(BaseMap):
         self.cvt_ESDF_to_voxels_slice(z)
         return self._read_esdf_slice(self._esdf_slice_n)
 
+    def query_esdf(self, xyz, interpolate=True, gradient=None, unknown_value=float("nan"), refresh=True):
+        """Batched ESDF queries at arbitrary points for planners (trajectory samples, collision checks, node expansions): returns
+        (dist f32[n], grad f32[n,3] or None, status u8[n]).  xyz [n,3] is in the frame of the submap the ESDF was last updated for (the frame
+        of is_pos_occupy / raycast).  interpolate=False reads the nearest voxel; interpolate=True interpolates the 8 corners of the cell
+        trilinearly, and gradient (default: the same as interpolate) adds the gradient of that interpolant.  status: 0 ok, 1 a needed voxel
+        is unknown (not observed / unallocated), 2 outside the volume; for those dist = unknown_value and grad = 0.  Flag 0x80 (torch input
+        only): the values come from an update that stopped before converging.  numpy in -> numpy out; torch CUDA tensors in -> torch tensors
+        on the same device, asynchronously, ordered with torch.cuda.current_stream (tsl_esdf_query_points_dev).
+        refresh=True first enqueues an incremental update with the parameters of the last update_esdf call (as cvt_ESDF_to_voxels_slice
+        does), so the answer reflects every frame so far; refresh=False reads the last update as it is.  Either needs an earlier update_esdf."""
+        mode = 1 if interpolate else 0
+        gradient = bool(interpolate) if gradient is None else bool(gradient)
+        if gradient and not mode:
+            raise ValueError("query_esdf: the gradient needs interpolate=True")
+        if refresh:
+            if not getattr(self, "_esdf_ever", False):
+                raise _lib.TslError("query_esdf: call update_esdf first (refresh repeats the last update's parameters)")
+            self.update_esdf(gamma=self._esdf_gamma, max_dist=self._esdf_max_dist, wait=False)
+        if _is_device_tensor(xyz):
+            torch = _torch()
+            x = xyz.reshape(-1, 3).contiguous().float()
+            n = x.shape[0]
+            dist = torch.empty(n, dtype=torch.float32, device=x.device)
+            grad = torch.empty((n, 3), dtype=torch.float32, device=x.device) if gradient else None
+            status = torch.empty(n, dtype=torch.uint8, device=x.device)
+            _lib.check(self.L.tsl_esdf_query_points_dev(self.h, mode, float(unknown_value), x.data_ptr(), n, dist.data_ptr(),
+                                                        None if grad is None else grad.data_ptr(), status.data_ptr(),
+                                                        torch.cuda.current_stream(x.device).cuda_stream))
+            return dist, grad, status
+        x = np.ascontiguousarray(np.asarray(xyz, dtype=np.float32).reshape(-1, 3))
+        n = x.shape[0]
+        dist = np.empty(n, np.float32)
+        grad = np.empty((n, 3), np.float32) if gradient else None
+        status = np.empty(n, np.uint8)
+        _lib.check(self.L.tsl_esdf_query_points(self.h, mode, float(unknown_value), _vp(x), n, _vp(dist), _vp(grad), _vp(status)))
+        return dist, grad, status
+
     def export_esdf_torch(self):
         """(indices int16[n,3], esdf f32[n]) as torch tensors on the device: zero-copy views of the map's staging buffer, valid until the
         next exporting call on this map (clone them to keep them)."""
