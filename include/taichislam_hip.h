@@ -275,6 +275,35 @@ int  tsl_esdf_query_points(tsl_tsdf* m, int mode, float unknown_value, const flo
 int  tsl_esdf_query_points_dev(tsl_tsdf* m, int mode, float unknown_value, const void* xyz_dev, int64_t n,
                                void* dist_dev, void* grad_dev, void* status_dev, void* user_stream);
 
+/* ---- view rendering (tsl_render.hip): what a camera at a pose would see of the TSDF -- depth, normal and colour per pixel.  It stands beside
+ * BaseMap.raycast (mapping_common.py:165-178; tsl_tsdf_query_raycast above), which steps a whole voxel at a time and returns the last stepped
+ * position; the reference has no renderer.  R (row-major) / T: the camera-to-map pose in the frame of tsl_tsdf_query_points (the active submap's;
+ * submap 0 on a global map), given as doubles and rounded to f32 once.  Definition (all f32, in this order):
+ *   pixel (u, v): dc = ((u - cx) / fx, (v - cy) / fy, 1), d = R dc -- NOT normalised: the ray parameter is the optical-axis depth, the unit of
+ *   the depth images.  Samples n = 0 .. S-1, S = (int)((t_max - t_min) / dt) + 1, at t_n = t_min + n * dt, p_n = T + t_n d.  A sample's value is the
+ *   trilinear interpolant of the stored TSDF over the 8 corners of the cell floor(p / voxel) (the interpolant of tsl_esdf_query_points mode 1);
+ *   it is KNOWN when all 8 are in the volume, in allocated bricks and observed.  Two consecutive known samples with s_prev > 0 >= s_n are a hit
+ *   (front face): t* = t_prev + dt * (s_prev / (s_prev - s_n)); with s_prev <= 0 < s_n a back face, which ends the ray.  An unknown sample only
+ *   forgets the previous one.
+ * Outputs, row-major [h][w]: depth f32 = t* (0 unless hit); normal (nullable) f32 x 3 = the gradient of the interpolant at T + t* d divided by
+ * its length, pointing from the surface into free space, in the map frame; rgb (nullable, textured maps only) f32 x 3 = the colour of the voxel
+ * rnd_i(p* / voxel) as the surface export reports it (0 when that voxel is unknown); status u8: 0 hit, 1 miss, 2 back face, | 0x40 a hit whose
+ * normal could not be formed (a corner of p*'s cell is unknown or the gradient is 0): the normal is 0.
+ * tsl_view_cfg: K row-major intrinsics (all 9 zero = the map's depth intrinsics), t_min / t_max (0 = the map's min / max_ray_length), dt (0 =
+ * 0.75 * voxel: about one voxel of path per sample at the corners of the field of view; the negative band behind a surface is internal_voxels
+ * deep, so a front face cannot be stepped over), flags bit 0 = evaluate every sample (by default a ray jumps over unallocated bricks and the
+ * space outside the volume; the result is the same bit for bit -- the A/B switch).
+ * TSL_ERR_ARG: a null handle / pose / cfg / depth / status, rgb on an untextured map, a non-finite pose, intrinsic or range, h or w outside
+ * 1 .. 32768, t_max <= t_min or dt <= 0 after the defaults, more than 2^24 samples per ray.
+ * The host form issues the queued frames, renders on the handle's stream, waits and copies back; the device form is ASYNCHRONOUS like
+ * tsl_tsdf_query_raycast_dev: launched on the handle's stream behind every queued frame, after the work queued on `user_stream`, which then
+ * waits for the result.  Neither reads or updates the ESDF. */
+typedef struct { double K[9]; int32_t h, w; float t_min, t_max, dt; int32_t flags; } tsl_view_cfg;
+int  tsl_tsdf_render_view(tsl_tsdf* m, const double R[9], const double T[3], const tsl_view_cfg* v,
+                          float* depth, float* normal, float* rgb, uint8_t* status);
+int  tsl_tsdf_render_view_dev(tsl_tsdf* m, const double R[9], const double T[3], const tsl_view_cfg* v,
+                              void* depth_dev, void* normal_dev, void* rgb_dev, void* status_dev, void* user_stream);
+
 /* backend knobs for A/B-ing kernel variants: name in
      "variant"  0|1: one global int64 atomic pair per ray step, 2 (default): brick-binned LDS accumulation
      "semantics" 0 (default): a frame's contributions to a voxel are summed exactly and applied once (order-free, oracle mode BATCHED);

@@ -52,6 +52,12 @@ class EsdfTotals(C.Structure):
         return {n: int(getattr(self, n)) for n, _ in self._fields_}
 
 
+class ViewCfg(C.Structure):
+    """tsl_view_cfg (tsl_tsdf_render_view): a zero K / t_min / t_max / dt means the map's default"""
+    _fields_ = [("K", C.c_double * 9), ("h", C.c_int32), ("w", C.c_int32), ("t_min", C.c_float), ("t_max", C.c_float), ("dt", C.c_float),
+                ("flags", C.c_int32)]
+
+
 class TslError(RuntimeError):
     pass
 
@@ -133,6 +139,8 @@ SIGNATURES = {
     "tsl_esdf_slice_dev": (C.c_int, [vp, C.POINTER(vp), C.POINTER(vp), pi32]),
     "tsl_esdf_query_points": (C.c_int, [vp, C.c_int, f32, vp, i64, vp, vp, vp]),
     "tsl_esdf_query_points_dev": (C.c_int, [vp, C.c_int, f32, vp, i64, vp, vp, vp, vp]),
+    "tsl_tsdf_render_view": (C.c_int, [vp, dp, dp, C.POINTER(ViewCfg), vp, vp, vp, vp]),
+    "tsl_tsdf_render_view_dev": (C.c_int, [vp, dp, dp, C.POINTER(ViewCfg), vp, vp, vp, vp, vp]),
     "tsl_tsdf_set_option": (C.c_int, [vp, C.c_char_p, C.c_int]),
     "tsl_tsdf_get_option": (C.c_int, [vp, C.c_char_p, C.POINTER(C.c_int)]),
     "tsl_tsdf_prof_enable": (C.c_int, [vp, C.c_int]),

@@ -7,7 +7,7 @@
 // mode 1 interpolates the 8 corners of the cell trilinearly in a fixed f32 order and returns the gradient of that interpolant, so that
 // tests/esdf_query_ref.py can restate it bit for bit in numpy.  Status per query: 0 ok, 1 a needed voxel is unknown, 2 a needed voxel is
 // outside the volume (or a coordinate is not finite); | 0x80 when the values come from an update that stopped before converging.
-#include "tsl_tsdf.hpp"
+#include "tsl_interp.hpp"      // lerp_f, cell_floor, the corner bricks and the interpolant: shared with tsl_render.hip
 
 namespace tsl {
 
@@ -19,11 +19,6 @@ namespace tsl {
 // relaxed magnitude (max_dist where the voxel was not observed at the last update)
 __device__ __forceinline__ float esdf_value(float t, float e, float gamma, float max_dist)
 { return fabsf(t) < gamma ? t : (float)sgn_f(t) * (e != e ? max_dist : fabsf(e)); }
-
-__device__ __forceinline__ float lerp_f(float a, float b, float t) { return a + t * (b - a); }
-
-// the cell index of a coordinate for mode 1: floor, clamped far outside any volume (the +1 corner cannot overflow; NaN lands on the clamp)
-__device__ __forceinline__ int cell_floor(float u) { return (int)fmaxf(fminf(floorf(u), 16777216.0f), -16777216.0f); }
 
 template <int MODE>
 __global__ void __launch_bounds__(256) k_esdf_query(MapDev M, int s, const float* __restrict__ esdf, float gamma, float max_dist, float vs, float unknown,
@@ -56,27 +51,12 @@ __global__ void __launch_bounds__(256) k_esdf_query(MapDev M, int s, const float
             const float f0 = u0 - (float)b0, f1 = u1 - (float)b1, f2 = u2 - (float)b2;
             int l000; const int bb = brick_of(M, b0, b1, b2, &l000);
             const int li = l000 >> 8, lj = (l000 >> 4) & 15, lk = l000 & 15;
-            // the +1 neighbour leaves the brick only from local index 15: look up the distinct bricks only (one lookup for 82 % of the cells)
-            const bool cx = li == 15, cy = lj == 15, cz = lk == 15;
-            const int dX = M.nbx * M.nbz, dY = M.nbz;
-            int P0 = T[bb], P1 = 0, P2 = 0, P3 = 0, P4 = 0, P5 = 0, P6 = 0, P7 = 0;           // corner c = p << 2 | q << 1 | r
-            if (cz) P1 = T[bb + 1];
-            if (cy) P2 = T[bb + dY];
-            if (cy && cz) P3 = T[bb + dY + 1];
-            if (cx) P4 = T[bb + dX];
-            if (cx && cz) P5 = T[bb + dX + 1];
-            if (cx && cy) P6 = T[bb + dX + dY];
-            if (cx && cy && cz) P7 = T[bb + dX + dY + 1];
-            if (!cz) { P1 = P0; P3 = P2; P5 = P4; P7 = P6; }
-            if (!cy) { P2 = P0; P3 = P1; P6 = P4; P7 = P5; }
-            if (!cx) { P4 = P0; P5 = P1; P6 = P2; P7 = P3; }
-            const int P[8] = { P0, P1, P2, P3, P4, P5, P6, P7 };
+            int P[8]; cell_bricks(M, T, bb, li, lj, lk, P);                                    // the distinct bricks only; corner c = p << 2 | q << 1 | r
             // all 24 gathers are issued before any is used: two dependent latencies per query (table, then data)
             uint32_t tw[8]; int ob[8]; float e[8];
 #pragma unroll
             for (int c = 0; c < 8; ++c) {
-                const int l = ((((li + (c >> 2)) & 15)) << 8) | (((lj + ((c >> 1) & 1)) & 15) << 4) | ((lk + (c & 1)) & 15);
-                const size_t v = (size_t)(P[c] < 0 ? 0 : P[c]) * TSL_BRK3 + l;
+                const size_t v = corner_voxel(P, c, li, lj, lk);
                 tw[c] = M.tw[v]; ob[c] = M.obs[v]; e[c] = esdf[v];
             }
             bool known = true;
@@ -88,12 +68,10 @@ __global__ void __launch_bounds__(256) k_esdf_query(MapDev M, int s, const float
             }
             st = EQ_UNKNOWN;
             if (known) {
-                // V[p << 2 | q << 1 | r] = c_pqr; the order of evaluation is the contract (tests/esdf_query_ref.py)
-                const float c000 = V[0], c001 = V[1], c010 = V[2], c011 = V[3], c100 = V[4], c101 = V[5], c110 = V[6], c111 = V[7];
-                d = lerp_f(lerp_f(lerp_f(c000, c100, f0), lerp_f(c010, c110, f0), f1), lerp_f(lerp_f(c001, c101, f0), lerp_f(c011, c111, f0), f1), f2);
-                g0 = lerp_f(lerp_f(c100 - c000, c110 - c010, f1), lerp_f(c101 - c001, c111 - c011, f1), f2) / vs;
-                g1 = lerp_f(lerp_f(c010 - c000, c110 - c100, f0), lerp_f(c011 - c001, c111 - c101, f0), f2) / vs;
-                g2 = lerp_f(lerp_f(c001 - c000, c101 - c100, f0), lerp_f(c011 - c010, c111 - c110, f0), f1) / vs;
+                // the order of evaluation is the contract (tsl_interp.hpp, tests/esdf_query_ref.py)
+                d = tri_value(V, f0, f1, f2);
+                tri_grad(V, f0, f1, f2, &g0, &g1, &g2);
+                g0 = g0 / vs; g1 = g1 / vs; g2 = g2 / vs;
                 st = 0;
             }
         }

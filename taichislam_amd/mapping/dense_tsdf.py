@@ -52,6 +52,38 @@ def _f64(a, n):
     return a
 
 
+def view_config(K=None, shape=(480, 640), t_min=None, t_max=None, step=None, skip=True):
+    """The tsl_view_cfg of DenseTSDF.render_view; None = the map's default (passed as 0).  Raises ValueError for values no view can have."""
+    cfg = _lib.ViewCfg()
+    if K is not None:
+        k = np.asarray(K, dtype=np.float64).reshape(-1)
+        if k.size != 9 or not np.isfinite(k).all() or not k.any():
+            raise ValueError("render_view: K must hold 9 finite values, not all zero")
+        cfg.K[:] = k.tolist()
+    h, w = (int(x) for x in shape)
+    if h <= 0 or w <= 0:
+        raise ValueError("render_view: shape must be (h, w) with h, w > 0")
+    cfg.h, cfg.w = h, w
+    for name, v in (("t_min", t_min), ("t_max", t_max), ("dt", step)):
+        if v is None:
+            continue
+        v = float(v)
+        if not math.isfinite(v) or (v <= 0.0 and name != "t_min") or v == 0.0:
+            raise ValueError(f"render_view: {name if name != 'dt' else 'step'} must be finite" + (" and positive" if name != "t_min" else " and not 0 (0 stands for the default)"))
+        setattr(cfg, name, v)
+    cfg.flags = 0 if skip else 1
+    return cfg
+
+
+def depth_to_mm(depth):
+    """A rendered depth image as the uint16 millimetre image recast_depth_to_map takes: rint(1000 * depth), 0 where there is no hit."""
+    if _is_device_tensor(depth):
+        torch = _torch()
+        return torch.clamp(torch.round(depth * 1000.0), 0, 65535).to(torch.int32).to(_DEPTH_DTYPES(torch)[1])
+    d = np.asarray(depth, dtype=np.float32)
+    return np.clip(np.rint(np.float32(1000.0) * d), 0, 65535).astype(np.uint16)
+
+
 class DenseTSDF(BaseMap):
     _prefix = "tsl_tsdf"
 
@@ -554,6 +586,39 @@ class DenseTSDF(BaseMap):
         hit = np.zeros(n, np.uint8); end = np.zeros((n, 3), np.float32); ln = np.zeros(n, np.float32)
         _lib.check(self.L.tsl_tsdf_query_raycast(self.h, _vp(pos), _vp(dir), float(max_dist), n, _vp(hit), _vp(end), _vp(ln)))
         return hit.astype(bool), end, ln
+
+    # ---- view rendering (tsl_render.hip; beside BaseMap.raycast, mapping_common.py:165-178) ----------
+    def render_view(self, R, T, K=None, shape=(480, 640), t_min=None, t_max=None, step=None, normals=True, colors=None, device=False, skip=True):
+        """What a camera at the camera-to-map pose (R, T) -- in the frame of is_pos_occupy / raycast: the active submap's, submap 0 on a global
+        map -- would see of the TSDF: returns (depth f32 [h, w], normal f32 [h, w, 3] or None, rgb f32 [h, w, 3] or None, status u8 [h, w]).
+        depth is the optical-axis depth of the first front face along the pixel's ray (the unit of the depth images; 0 where there is none), found
+        by sampling the trilinear interpolant of the TSDF every `step` metres of depth between t_min and t_max and refining the zero crossing
+        linearly; the normal is the normalised gradient of the interpolant there (map frame, pointing into free space), rgb the colour of the
+        nearest voxel.  status: 0 hit, 1 miss, 2 the ray met a surface from behind (depth 0), | 0x40 a hit without a normal (it touches
+        unobserved voxels).  K: row-major intrinsics of the view (default: the map's depth intrinsics); t_min / t_max default to the map's
+        min / max_ray_length, step to 0.75 voxel; colors=None means "if the map is textured".  skip=False evaluates every sample instead of
+        jumping over unallocated bricks: the same image bit for bit, slower (the A/B switch).  device=True returns torch tensors on the map's
+        device, asynchronously, ordered with torch.cuda.current_stream (tsl_tsdf_render_view_dev); otherwise numpy arrays."""
+        cfg = view_config(K, shape, t_min, t_max, step, skip)
+        colors = bool(self.enable_texture) if colors is None else bool(colors)
+        r, t = _dptr(R, 9)[1], _dptr(T, 3)[1]
+        h, w = cfg.h, cfg.w
+        if device:
+            torch = _torch()
+            dev = torch.device(f"cuda:{self.device}")
+            depth = torch.empty((h, w), dtype=torch.float32, device=dev)
+            normal = torch.empty((h, w, 3), dtype=torch.float32, device=dev) if normals else None
+            rgb = torch.empty((h, w, 3), dtype=torch.float32, device=dev) if colors else None
+            status = torch.empty((h, w), dtype=torch.uint8, device=dev)
+            _lib.check(self.L.tsl_tsdf_render_view_dev(self.h, r, t, C.byref(cfg), depth.data_ptr(), None if normal is None else normal.data_ptr(),
+                                                       None if rgb is None else rgb.data_ptr(), status.data_ptr(), torch.cuda.current_stream(dev).cuda_stream))
+            return depth, normal, rgb, status
+        depth = np.empty((h, w), np.float32)
+        normal = np.empty((h, w, 3), np.float32) if normals else None
+        rgb = np.empty((h, w, 3), np.float32) if colors else None
+        status = np.empty((h, w), np.uint8)
+        _lib.check(self.L.tsl_tsdf_render_view(self.h, r, t, C.byref(cfg), _vp(depth), _vp(normal), _vp(rgb), _vp(status)))
+        return depth, normal, rgb, status
 
     # ---- ESDF (definition from the legacy dense_esdf.py:228-333; see DESIGN.md) -----------------------------------
     def update_esdf(self, gamma=None, max_dist=None, wait=True):
