@@ -304,6 +304,56 @@ int  tsl_tsdf_render_view(tsl_tsdf* m, const double R[9], const double T[3], con
 int  tsl_tsdf_render_view_dev(tsl_tsdf* m, const double R[9], const double T[3], const tsl_view_cfg* v,
                               void* depth_dev, void* normal_dev, void* rgb_dev, void* status_dev, void* user_stream);
 
+/* ---- frame-to-model alignment (tsl_align.hip): a depth frame against the TSDF, Gauss-Newton on the signed distance -- minimise the sum of
+ * s(R p_i + T)^2 over the camera-to-map pose (Bylow et al. 2013; Canelhas' SDF tracker).  The reference takes its poses from a VIO and has no
+ * tracker.  R (row-major) / T: the camera-to-map pose in the frame of tsl_tsdf_query_points (the active submap's; submap 0 on a global map),
+ * given as doubles and rounded to f32 once.  depth: uint16 millimetres [h][w], C-contiguous.
+ * Definition (all f32, no contraction, in this order).  Visited pixels (i, j) = (ii * stride, jj * stride), ii < ceil(w /
+ * stride), jj < ceil(h / stride); each lands in exactly one bucket, tested in this order:
+ *   n_gate     d == 0, (float)d > d_max * 1000 or (float)d < d_min * 1000.  Otherwise dep = (float)d / 1000, px = ((float)i - cx) * dep / fx,
+ *              py = ((float)j - cy) * dep / fy, pz = dep and p[a] = ((R[a][0] * px + R[a][1] * py) + R[a][2] * pz) + T[a]
+ *   n_unknown  the sample at p is not KNOWN in the sense of tsl_tsdf_render_view (8 corners in the volume, in allocated bricks and observed, p
+ *              finite).  Otherwise s = the trilinear interpolant, g = its gradient per metre (the expressions of tsl_esdf_query_points mode 1)
+ *   n_far      |s| > r_max
+ *   n_grad     gg = (g0 * g0 + g1 * g1) + g2 * g2 is 0 or > g_max * g_max
+ *   n_used     c = p x g, J = (g0, g1, g2, c0, c1, c2), wgt = huber > 0 && |s| > huber ? huber / |s| : 1, wJ[a] = wgt * J[a]; the 28 products
+ *              H_ab = wJ[a] * J[b] (a <= b, row-major upper triangle), b_a = wJ[a] * s, e = (wgt * s) * s
+ * Every product x is added as the integer rint(x * 2^20) (round half to even) into an int64 sum, so the sums are the same for any schedule.
+ * tsl_align_cfg: K row-major intrinsics (all 9 zero = the map's depth intrinsics), stride >= 1, d_min / d_max (0 = the map's min / max_ray_length),
+ * r_max (0 = internal_voxels * voxel, the depth of the negative band), g_max (0 = 4), huber (0 = off), flags bit 0 = counts only: the
+ * products and their reduction are left out, H, b and e are 0 (what the gathers alone cost: the A/B switch of tools/bench_track.py; a tracker needs 0).
+ * The call is refused unless M^2 * 2^20 * visited <= 2^62, M = max(2 L g_max, g_max, r_max), L the largest absolute coordinate of the volume: no
+ * sum can overflow.
+ * tsl_tsdf_align_linearize issues the queued frames, runs on the handle's stream, waits and returns the 33 integers.  The device form is
+ * ASYNCHRONOUS like tsl_tsdf_render_view_dev: sums_dev (int64[40]: the 33 integers in the order of tsl_align_sums, the rest 0) is zeroed and
+ * filled on the handle's stream behind every queued frame, after the work queued on `user_stream`, which then waits for the result.
+ * Step (pure host, float64, fixed order, no libm call but sqrt): Hd = H * 2^-20, bd = b * 2^-20, Hd_aa += damping * Hd_aa, Cholesky L L^T
+ * without pivoting; a pivot <= 0 or not finite (or a non-finite solution) is singular: *singular = 1 and xi = 0; else xi = (v, omega) = -Hd^-1 bd.
+ * Retraction (pure host, in place): the Cayley map, a = omega / 2, C = ((1 - a.a) I + 2 a a^T + 2 [a]x) / (1 + a.a); R <- C R, T <- C T + v.
+ * Tracking: up to 4 levels (stride, iters), at most 64 iterations in all.  An iteration linearises at the current pose, solves and retracts; a
+ * level ends early when sqrt(|v|^2 + |omega|^2) < min_step.  status 0: the last level ended by the threshold, 1: its iterations were exhausted,
+ * 2: lost -- a linearisation had n_used < min_used (0 = 6), 3: singular.  On 2 and 3 the pose returned is the last one that gave a step, or the
+ * guess.  Every linearisation leaves a record: the float64 pose, the sums, xi (0 where there was no step); `iterations` counts the records.
+ * tsl_tsdf_track_depth_dev first makes the handle's stream wait for the work queued on `user_stream`, then runs as the host form and returns
+ * when it is done.
+ * TSL_ERR_ARG (the text names the entry point): a null handle / pose / cfg / depth / out, a non-finite pose, intrinsic or parameter, h or w outside
+ * 1 .. 32768, stride < 1, d_max <= d_min after the defaults, a negative r_max / g_max / huber / damping / min_step, the overflow bound, more
+ * than 4 levels or 64 iterations. */
+typedef struct { double K[9]; int32_t h, w, stride; float d_min, d_max, r_max, g_max, huber; int32_t flags; } tsl_align_cfg;
+typedef struct { int64_t H[21], b[6], e, n_used, n_gate, n_unknown, n_far, n_grad; } tsl_align_sums;
+typedef struct { int32_t n_levels, stride[4], iters[4], min_used; double min_step, damping; } tsl_track_cfg;
+typedef struct { double R[9], T[3], xi[6]; tsl_align_sums sums; } tsl_track_iter;
+typedef struct { int32_t status, iterations; tsl_track_iter it[64]; } tsl_track_report;
+int  tsl_tsdf_align_linearize(tsl_tsdf* m, const double R[9], const double T[3], const tsl_align_cfg* c, const uint16_t* depth, tsl_align_sums* out);
+int  tsl_tsdf_align_linearize_dev(tsl_tsdf* m, const double R[9], const double T[3], const tsl_align_cfg* c, const void* depth_dev,
+                                  void* sums_dev, void* user_stream);
+int  tsl_align_solve(const tsl_align_sums* s, double damping, double xi[6], int32_t* singular);
+int  tsl_pose_retract(const double xi[6], double R[9], double T[3]);
+int  tsl_tsdf_track_depth(tsl_tsdf* m, const double R0[9], const double T0[3], const tsl_align_cfg* c, const tsl_track_cfg* t, const uint16_t* depth,
+                          double R_out[9], double T_out[3], tsl_track_report* rep);
+int  tsl_tsdf_track_depth_dev(tsl_tsdf* m, const double R0[9], const double T0[3], const tsl_align_cfg* c, const tsl_track_cfg* t, const void* depth_dev,
+                              double R_out[9], double T_out[3], tsl_track_report* rep, void* user_stream);
+
 /* backend knobs for A/B-ing kernel variants: name in
      "variant"  0|1: one global int64 atomic pair per ray step, 2 (default): brick-binned LDS accumulation
      "semantics" 0 (default): a frame's contributions to a voxel are summed exactly and applied once (order-free, oracle mode BATCHED);

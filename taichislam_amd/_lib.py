@@ -58,6 +58,30 @@ class ViewCfg(C.Structure):
                 ("flags", C.c_int32)]
 
 
+class AlignCfg(C.Structure):
+    """tsl_align_cfg (tsl_tsdf_align_linearize, tsl_tsdf_track_depth): a zero K / d_min / d_max / r_max / g_max means the default, huber 0 = off"""
+    _fields_ = [("K", C.c_double * 9), ("h", C.c_int32), ("w", C.c_int32), ("stride", C.c_int32), ("d_min", C.c_float), ("d_max", C.c_float),
+                ("r_max", C.c_float), ("g_max", C.c_float), ("huber", C.c_float), ("flags", C.c_int32)]
+
+
+class AlignSums(C.Structure):
+    """tsl_align_sums: the normal equations in 2^-20 fixed point and the five pixel counts, 33 x int64"""
+    _fields_ = [("H", C.c_int64 * 21), ("b", C.c_int64 * 6)] + [(n, C.c_int64) for n in ("e", "n_used", "n_gate", "n_unknown", "n_far", "n_grad")]
+
+
+class TrackCfg(C.Structure):
+    _fields_ = [("n_levels", C.c_int32), ("stride", C.c_int32 * 4), ("iters", C.c_int32 * 4), ("min_used", C.c_int32), ("min_step", C.c_double),
+                ("damping", C.c_double)]
+
+
+class TrackIter(C.Structure):
+    _fields_ = [("R", C.c_double * 9), ("T", C.c_double * 3), ("xi", C.c_double * 6), ("sums", AlignSums)]
+
+
+class TrackReport(C.Structure):
+    _fields_ = [("status", C.c_int32), ("iterations", C.c_int32), ("it", TrackIter * 64)]
+
+
 class TslError(RuntimeError):
     pass
 
@@ -141,6 +165,12 @@ SIGNATURES = {
     "tsl_esdf_query_points_dev": (C.c_int, [vp, C.c_int, f32, vp, i64, vp, vp, vp, vp]),
     "tsl_tsdf_render_view": (C.c_int, [vp, dp, dp, C.POINTER(ViewCfg), vp, vp, vp, vp]),
     "tsl_tsdf_render_view_dev": (C.c_int, [vp, dp, dp, C.POINTER(ViewCfg), vp, vp, vp, vp, vp]),
+    "tsl_tsdf_align_linearize": (C.c_int, [vp, dp, dp, C.POINTER(AlignCfg), vp, C.POINTER(AlignSums)]),
+    "tsl_tsdf_align_linearize_dev": (C.c_int, [vp, dp, dp, C.POINTER(AlignCfg), vp, vp, vp]),
+    "tsl_align_solve": (C.c_int, [C.POINTER(AlignSums), C.c_double, dp, pi32]),
+    "tsl_pose_retract": (C.c_int, [dp, dp, dp]),
+    "tsl_tsdf_track_depth": (C.c_int, [vp, dp, dp, C.POINTER(AlignCfg), C.POINTER(TrackCfg), vp, dp, dp, C.POINTER(TrackReport)]),
+    "tsl_tsdf_track_depth_dev": (C.c_int, [vp, dp, dp, C.POINTER(AlignCfg), C.POINTER(TrackCfg), vp, dp, dp, C.POINTER(TrackReport), vp]),
     "tsl_tsdf_set_option": (C.c_int, [vp, C.c_char_p, C.c_int]),
     "tsl_tsdf_get_option": (C.c_int, [vp, C.c_char_p, C.POINTER(C.c_int)]),
     "tsl_tsdf_prof_enable": (C.c_int, [vp, C.c_int]),

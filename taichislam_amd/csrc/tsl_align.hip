@@ -1,0 +1,403 @@
+// tsl_align.hip -- frame-to-model alignment: a depth frame against the TSDF, Gauss-Newton on the signed distance (Bylow et al., "Real-Time Camera
+// Tracking and 3D Reconstruction Using Signed Distance Functions", RSS 2013; Canelhas et al., "SDF Tracker", IROS 2013): minimise the sum of
+// s(R p_i + T)^2 over the camera-to-map pose, s the trilinear interpolant of the stored TSDF (tsl_interp.hpp), p_i the back-projected pixels.  The
+// reference takes its poses from a VIO and has no tracker; tsl_render.hip renders the model image, this file consumes a frame against the model.
+//
+// Definition (tests/track_ref.py restates it in numpy and every integer must equal it).  All f32, no contraction, in the
+// written order.  Visited pixels (i, j) = (ii * stride, jj * stride).  A pixel with depth d (uint16 millimetres) falls into exactly one bucket:
+//   gate     d == 0, (float)d > d_max * 1000 or (float)d < d_min * 1000 (the comparisons of k_voxelize_depth, tsl_tsdf.hip); otherwise
+//            dep = (float)d / 1000, px = ((float)i - cx) * dep / fx, py = ((float)j - cy) * dep / fy, pz = dep, p[a] = ((R[a][0] px + R[a][1] py) + R[a][2] pz) + T[a]
+//   unknown  the sample at p is not KNOWN (section 4.7); otherwise s = tri_value, g = tri_grad / vs
+//   far      |s| > r_max
+//   grad     gg = (g0 g0 + g1 g1) + g2 g2 is 0 or > g_max * g_max
+//   used     c = p x g, J = (g, c), wgt = huber > 0 && |s| > huber ? huber / |s| : 1, wJ = wgt J; the 28 products H_ab = wJ[a] J[b] (a <= b), b_a = wJ[a] s,
+//            e = (wgt s) s
+// Every product x is added as the integer rint(x * 2^20) (round half to even) into int64 sums: integer sums do not depend on the order of
+// the additions, so the 33 integers are the same for any schedule.
+//
+// One lane per visited pixel, a wave covers an 8 x 8 tile of them and a workgroup 16 x 16 (the tiling of k_render_view).  The 28 sums are reduced in
+// the wave by a halving butterfly -- at the step over lane bit b a lane keeps one half of its values and hands the other half to its partner, 16 + 8
+// + 4 + 2 + 1 + 1 = 32 exchanges instead of 28 x 6 -- the five counts by ballots, then across the four waves through LDS; one 64-bit integer
+// atomic per non-zero sum per workgroup.  No float atomics.  flags bit 0 leaves the products and their reduction out (H, b, e = 0, the counts as
+// usual): what the gathers cost alone (tools/bench_track.py).
+#include <cmath>
+#include "tsl_interp.hpp"
+
+namespace tsl {
+
+#define AL_SLOTS 40                    // int64 slots of the device accumulator: 33 used (tsl_align_sums), the rest stay 0
+#define AL_NPROD 28
+#define AL_SCALE 1048576.0f            // 2^20
+#define AL_USED 0
+#define AL_GATE 1
+#define AL_UNKNOWN 2
+#define AL_FAR 3
+#define AL_GRAD 4
+
+struct AlignDev {
+    float R[9], T[3];                  // camera-to-map pose in the frame of the point queries, rounded to f32 once
+    float fx, fy, cx, cy, vs;
+    float thr_min, thr_max;            // the depth gate in millimetres
+    float r_max, gm2, huber;           // gm2 = g_max * g_max
+    int h, w, stride, hh, ww;          // image size; visited rows / columns
+    int flags;                         // bit 0: counts only
+};
+
+// rint(x * 2^20) as an integer.  The product is exact in f32 (a power of two; the overflow refusal keeps it far below 2^63), so this is
+// (int64) rint((double)x * 2^20).
+__device__ __forceinline__ long long al_fix(float x)
+{
+    const float q = rintf(x * AL_SCALE);
+    if (fabsf(q) < 2147483648.0f) return (long long)(int)q;
+    return (long long)q;
+}
+
+// one halving step of the wave reduction: v[0 .. N-1] of this lane and of lane ^ D become v[0 .. N/2-1], the sums of the half this lane keeps
+template <int N, int D>
+__device__ __forceinline__ void al_halve(long long (&v)[32], int lane)
+{
+    const bool up = (lane & D) != 0;
+#pragma unroll
+    for (int i = 0; i < N / 2; ++i) {
+        const long long keep = up ? v[i + N / 2] : v[i], send = up ? v[i] : v[i + N / 2];
+        v[i] = keep + __shfl_xor(send, D);
+    }
+}
+
+__global__ void __launch_bounds__(256) k_align_linearize(MapDev M, int s, AlignDev A, const uint16_t* __restrict__ depth, long long* __restrict__ acc)
+{
+    __shared__ long long sm[4][32];
+    __shared__ int sc[4][8];
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int ii = blockIdx.x * 16 + (wave & 1) * 8 + (lane & 7), jj = blockIdx.y * 16 + (wave >> 1) * 8 + (lane >> 3);
+    const int* __restrict__ T = M.table + (size_t)s * M.nb3;
+    int bucket = -1;                                              // not a visited pixel
+    float sv = 0.0f, g0 = 0.0f, g1 = 0.0f, g2 = 0.0f, p[3] = { 0.0f, 0.0f, 0.0f };
+    if (ii < A.ww && jj < A.hh) {
+        const int i = ii * A.stride, j = jj * A.stride;
+        const uint16_t d = depth[(size_t)j * A.w + i];
+        const float df = (float)d;
+        bucket = AL_GATE;
+        if (d != 0 && !(df > A.thr_max) && !(df < A.thr_min)) {
+            const float dep = df / 1000.0f;
+            const float px = ((float)i - A.cx) * dep / A.fx, py = ((float)j - A.cy) * dep / A.fy, pz = dep;
+            float u[3]; int b[3];
+#pragma unroll
+            for (int a = 0; a < 3; ++a) {
+                p[a] = ((A.R[a * 3] * px + A.R[a * 3 + 1] * py) + A.R[a * 3 + 2] * pz) + A.T[a];
+                u[a] = p[a] / A.vs; b[a] = cell_floor(u[a]);
+            }
+            bucket = AL_UNKNOWN;
+            float V[8];
+            if (isfinite(p[0]) && isfinite(p[1]) && isfinite(p[2]) && tsdf_read_cell(M, T, b[0], b[1], b[2], V)) {
+                const float f0 = u[0] - (float)b[0], f1 = u[1] - (float)b[1], f2 = u[2] - (float)b[2];
+                sv = tri_value(V, f0, f1, f2);
+                tri_grad(V, f0, f1, f2, &g0, &g1, &g2);
+                g0 = g0 / A.vs; g1 = g1 / A.vs; g2 = g2 / A.vs;
+                const float gg = (g0 * g0 + g1 * g1) + g2 * g2;
+                bucket = fabsf(sv) > A.r_max ? AL_FAR : (gg == 0.0f || gg > A.gm2) ? AL_GRAD : AL_USED;
+            }
+        }
+    }
+    const bool used = bucket == AL_USED;
+    long long v[32];
+#pragma unroll
+    for (int k = 0; k < 32; ++k) v[k] = 0;
+    const bool sums = !(A.flags & 1);                             // the A/B switch: without the products and their reduction only the counts are formed
+    if (used && sums) {
+        const float J[6] = { g0, g1, g2, p[1] * g2 - p[2] * g1, p[2] * g0 - p[0] * g2, p[0] * g1 - p[1] * g0 };
+        const float as = fabsf(sv);
+        const float wgt = (A.huber > 0.0f && as > A.huber) ? A.huber / as : 1.0f;
+        float wJ[6];
+#pragma unroll
+        for (int a = 0; a < 6; ++a) wJ[a] = wgt * J[a];
+        int k = 0;
+#pragma unroll
+        for (int a = 0; a < 6; ++a)
+#pragma unroll
+            for (int c = a; c < 6; ++c) v[k++] = al_fix(wJ[a] * J[c]);
+#pragma unroll
+        for (int a = 0; a < 6; ++a) v[21 + a] = al_fix(wJ[a] * sv);
+        v[27] = al_fix((wgt * sv) * sv);
+    }
+    // the wave's sums: after the five halving steps lane l holds sum number l >> 1 over its half of the wave, the last step adds the other half
+    const unsigned long long mu = __ballot(used);
+    if (mu && sums) {
+        al_halve<32, 32>(v, lane); al_halve<16, 16>(v, lane); al_halve<8, 8>(v, lane); al_halve<4, 4>(v, lane); al_halve<2, 2>(v, lane);
+        v[0] += __shfl_xor(v[0], 1);
+    }
+    if (!(lane & 1)) sm[wave][lane >> 1] = v[0];
+    const unsigned long long mg = __ballot(bucket == AL_GATE), mk = __ballot(bucket == AL_UNKNOWN), mf = __ballot(bucket == AL_FAR), mr = __ballot(bucket == AL_GRAD);
+    if (lane == 0) { sc[wave][AL_USED] = popc64(mu); sc[wave][AL_GATE] = popc64(mg); sc[wave][AL_UNKNOWN] = popc64(mk); sc[wave][AL_FAR] = popc64(mf); sc[wave][AL_GRAD] = popc64(mr); }
+    __syncthreads();
+    const int t = threadIdx.x;
+    if (t < AL_NPROD + 5) {
+        long long sum;
+        if (t < AL_NPROD) sum = (sm[0][t] + sm[1][t]) + (sm[2][t] + sm[3][t]);
+        else { const int c = t - AL_NPROD; sum = (long long)((sc[0][c] + sc[1][c]) + (sc[2][c] + sc[3][c])); }
+        if (sum != 0) __hip_atomic_fetch_add(acc + t, sum, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+}
+
+static bool al_finite(const double* a, int n) { for (int i = 0; i < n; ++i) if (!std::isfinite(a[i])) return false; return true; }
+
+// the checks and defaults every form shares; `stride` replaces the configuration's (the levels of the tracker)
+static int align_check(tsl_tsdf* m, const double R[9], const double T[3], const tsl_align_cfg* c, const void* depth, const void* out, int stride,
+                       AlignDev* A, const char* who)
+{
+    const std::string w(who);
+    TSL_REQUIRE(m, w + ": null handle");
+    TSL_REQUIRE(R && T && c && depth && out, w + ": null argument");
+    TSL_REQUIRE(al_finite(R, 9) && al_finite(T, 3), w + ": the pose is not finite");
+    TSL_REQUIRE(al_finite(c->K, 9), w + ": an intrinsic is not finite");
+    TSL_REQUIRE(std::isfinite(c->d_min) && std::isfinite(c->d_max) && std::isfinite(c->r_max) && std::isfinite(c->g_max) && std::isfinite(c->huber),
+                w + ": d_min / d_max / r_max / g_max / huber is not finite");
+    TSL_REQUIRE(c->h > 0 && c->w > 0 && c->h <= 32768 && c->w <= 32768, w + ": the image size must be 1 .. 32768 per side");
+    TSL_REQUIRE(stride >= 1, w + ": stride must be at least 1");
+    TSL_REQUIRE(!(c->r_max < 0.0f) && !(c->g_max < 0.0f) && !(c->huber < 0.0f), w + ": r_max, g_max and huber must not be negative");
+    for (int i = 0; i < 9; ++i) A->R[i] = (float)R[i];
+    for (int i = 0; i < 3; ++i) A->T[i] = (float)T[i];
+    bool zero = true; for (int i = 0; i < 9; ++i) zero = zero && c->K[i] == 0.0;
+    if (zero) { A->fx = m->P.fx; A->fy = m->P.fy; A->cx = m->P.cx; A->cy = m->P.cy; }           // the map's depth intrinsics
+    else { A->fx = (float)c->K[0]; A->fy = (float)c->K[4]; A->cx = (float)c->K[2]; A->cy = (float)c->K[5]; }
+    A->vs = m->P.vs;
+    const double dmin = c->d_min != 0.0f ? (double)c->d_min : m->cfg.min_ray_length, dmax = c->d_max != 0.0f ? (double)c->d_max : m->cfg.max_ray_length;
+    TSL_REQUIRE(dmax > dmin, w + ": d_max must exceed d_min");
+    A->thr_min = (float)(dmin * 1000.0); A->thr_max = (float)(dmax * 1000.0);                     // as tsl_tsdf_create forms the integrator's gate
+    A->r_max = c->r_max != 0.0f ? c->r_max : (float)((double)m->cfg.internal_voxels * m->cfg.voxel_scale);
+    const float gmax = c->g_max != 0.0f ? c->g_max : 4.0f;
+    A->gm2 = gmax * gmax;
+    A->huber = c->huber;
+    A->h = c->h; A->w = c->w; A->stride = stride; A->flags = c->flags;
+    A->hh = (int)(((long long)c->h + stride - 1) / stride); A->ww = (int)(((long long)c->w + stride - 1) / stride);      // a stride near INT_MAX must not wrap
+    // no sum can overflow: a used pixel has |g_a| <= g_max, |p_a| <= L (its cell is in the volume), so |c_a| <= 2 L g_max, and |s| <= r_max;
+    // wgt <= 1.  Every product is at most M^2 in magnitude, M = max(2 L g_max, g_max, r_max), every addend at most M^2 2^20 + 1/2.
+    const double L = (double)(m->M.hN > m->M.hNz ? m->M.hN : m->M.hNz) * m->cfg.voxel_scale;
+    double Mx = 2.0 * L * (double)gmax;
+    if ((double)gmax > Mx) Mx = (double)gmax;
+    if ((double)A->r_max > Mx) Mx = (double)A->r_max;
+    const double visited = (double)A->hh * (double)A->ww;
+    TSL_REQUIRE(Mx * Mx * 1048576.0 * visited <= 4611686018427387904.0, w + ": the sums could overflow (max(2 L g_max, r_max)^2 * 2^20 * visited pixels exceeds 2^62)");
+    return TSL_OK;
+}
+
+// zeroes the accumulator and launches, both on q
+static int align_launch(tsl_tsdf* m, hipStream_t q, const AlignDev& A, const uint16_t* depth, long long* acc)
+{
+    TSL_HIP(hipMemsetAsync(acc, 0, AL_SLOTS * sizeof(long long), q));
+    hipLaunchKernelGGL(k_align_linearize, dim3((unsigned)((A.ww + 15) / 16), (unsigned)((A.hh + 15) / 16)), dim3(256), 0, q, m->M,
+                       m->cfg.is_global_map ? 0 : m->active, A, depth, acc);
+    TSL_HIP(hipGetLastError());
+    return TSL_OK;
+}
+
+static long long* al_pinned(tsl_tsdf* m) { return reinterpret_cast<long long*>(m->h_ints + 128); }      // the upper part of the pinned scratch: 40 x int64
+
+// one linearisation on q with the result on the host: launch, copy back through the pinned buffer, wait
+static int align_run(tsl_tsdf* m, hipStream_t q, const AlignDev& A, const uint16_t* depth_dev, long long* acc, tsl_align_sums* out)
+{
+    int rc = align_launch(m, q, A, depth_dev, acc); if (rc) return rc;
+    TSL_HIP(hipMemcpyAsync(al_pinned(m), acc, sizeof(tsl_align_sums), hipMemcpyDeviceToHost, q));
+    TSL_HIP(hipStreamSynchronize(q));
+    std::memcpy(out, al_pinned(m), sizeof(tsl_align_sums));
+    return TSL_OK;
+}
+
+// the accumulator and (host form) the staged image in the export staging buffer: [40 x int64 | pad to 512 | depth]
+static int align_stage(tsl_tsdf* m, hipStream_t q, const tsl_align_cfg* c, const uint16_t* depth_host, long long** acc, const uint16_t** depth_dev)
+{
+    const size_t bytes = (size_t)c->h * c->w * sizeof(uint16_t);
+    int rc = grow(&m->xbuf, &m->xbuf_bytes, 512 + (depth_host ? bytes : 0) + 64); if (rc) return rc;
+    *acc = (long long*)m->xbuf;
+    if (depth_host) {
+        TSL_HIP(hipMemcpyAsync((char*)m->xbuf + 512, depth_host, bytes, hipMemcpyHostToDevice, q));
+        *depth_dev = (const uint16_t*)((char*)m->xbuf + 512);
+    }
+    return TSL_OK;
+}
+
+// ---- the step and the retraction: host code, float64, in this order (tests/track_ref.py restates both) ----
+
+static void al_system(const tsl_align_sums* s, double damping, double Hm[6][6], double b[6])
+{
+    int k = 0;
+    for (int a = 0; a < 6; ++a) for (int c = a; c < 6; ++c) { const double x = (double)s->H[k++] * (1.0 / 1048576.0); Hm[a][c] = x; Hm[c][a] = x; }
+    for (int a = 0; a < 6; ++a) { b[a] = (double)s->b[a] * (1.0 / 1048576.0); Hm[a][a] += damping * Hm[a][a]; }
+}
+
+// xi = -H^-1 b by Cholesky L L^T without pivoting, column by column; false (xi = 0) when a pivot is <= 0 or not finite
+static bool al_solve(const tsl_align_sums* s, double damping, double xi[6])
+{
+    double Hm[6][6], b[6], Lm[6][6], y[6];
+    al_system(s, damping, Hm, b);
+    for (int a = 0; a < 6; ++a) xi[a] = 0.0;
+    for (int j = 0; j < 6; ++j) {
+        double d = Hm[j][j];
+        for (int k = 0; k < j; ++k) d -= Lm[j][k] * Lm[j][k];
+        if (!(d > 0.0) || !std::isfinite(d)) return false;
+        Lm[j][j] = std::sqrt(d);
+        for (int i = j + 1; i < 6; ++i) {
+            double t = Hm[i][j];
+            for (int k = 0; k < j; ++k) t -= Lm[i][k] * Lm[j][k];
+            Lm[i][j] = t / Lm[j][j];
+        }
+    }
+    for (int i = 0; i < 6; ++i) {                                  // L y = -b
+        double t = -b[i];
+        for (int k = 0; k < i; ++k) t -= Lm[i][k] * y[k];
+        y[i] = t / Lm[i][i];
+    }
+    double x[6];
+    for (int i = 5; i >= 0; --i) {                                 // L^T x = y
+        double t = y[i];
+        for (int k = i + 1; k < 6; ++k) t -= Lm[k][i] * x[k];
+        x[i] = t / Lm[i][i];
+    }
+    for (int a = 0; a < 6; ++a) if (!std::isfinite(x[a])) return false;
+    for (int a = 0; a < 6; ++a) xi[a] = x[a];
+    return true;
+}
+
+// the Cayley map of omega = xi[3..5]: R <- C R, T <- C T + v
+static void al_retract(const double xi[6], double R[9], double T[3])
+{
+    const double a[3] = { xi[3] * 0.5, xi[4] * 0.5, xi[5] * 0.5 };
+    const double aa = (a[0] * a[0] + a[1] * a[1]) + a[2] * a[2], den = 1.0 + aa;
+    const double S[3][3] = { { 0.0, -a[2], a[1] }, { a[2], 0.0, -a[0] }, { -a[1], a[0], 0.0 } };
+    double Cm[3][3], Rn[9], Tn[3];
+    for (int i = 0; i < 3; ++i) for (int j = 0; j < 3; ++j) Cm[i][j] = (((i == j ? 1.0 - aa : 0.0) + (2.0 * a[i]) * a[j]) + 2.0 * S[i][j]) / den;
+    for (int i = 0; i < 3; ++i) {
+        for (int j = 0; j < 3; ++j) Rn[i * 3 + j] = (Cm[i][0] * R[j] + Cm[i][1] * R[3 + j]) + Cm[i][2] * R[6 + j];
+        Tn[i] = ((Cm[i][0] * T[0] + Cm[i][1] * T[1]) + Cm[i][2] * T[2]) + xi[i];
+    }
+    for (int i = 0; i < 9; ++i) R[i] = Rn[i];
+    for (int i = 0; i < 3; ++i) T[i] = Tn[i];
+}
+
+static int track_check(const tsl_track_cfg* t, const char* who)
+{
+    const std::string w(who);
+    TSL_REQUIRE(t, w + ": null argument");
+    TSL_REQUIRE(t->n_levels >= 1 && t->n_levels <= 4, w + ": 1 .. 4 levels");
+    int total = 0;
+    for (int l = 0; l < t->n_levels; ++l) {
+        TSL_REQUIRE(t->stride[l] >= 1, w + ": stride must be at least 1");
+        TSL_REQUIRE(t->iters[l] >= 0 && t->iters[l] <= 64, w + ": at most 64 iterations");
+        total += t->iters[l];
+    }
+    TSL_REQUIRE(total <= 64, w + ": at most 64 iterations");
+    TSL_REQUIRE(t->min_used >= 0, w + ": min_used must not be negative");
+    TSL_REQUIRE(std::isfinite(t->min_step) && std::isfinite(t->damping) && !(t->min_step < 0.0) && !(t->damping < 0.0), w + ": min_step and damping must be finite and not negative");
+    return TSL_OK;
+}
+
+// the iteration; the depth image is on the device, q has been ordered behind whatever produced it
+static int track_run(tsl_tsdf* m, hipStream_t q, const double R0[9], const double T0[3], const tsl_align_cfg* c, const tsl_track_cfg* t, const uint16_t* depth_dev,
+                     long long* acc, double R_out[9], double T_out[3], tsl_track_report* rep, const char* who)
+{
+    double R[9], T[3], Rl[9], Tl[3];                               // the current pose; the last one that gave a step
+    std::memcpy(R, R0, sizeof(R)); std::memcpy(T, T0, sizeof(T)); std::memcpy(Rl, R0, sizeof(Rl)); std::memcpy(Tl, T0, sizeof(Tl));
+    const int64_t min_used = t->min_used > 0 ? t->min_used : 6;
+    int n = 0, status = 1;
+    bool failed = false;
+    for (int l = 0; l < t->n_levels && !failed; ++l) {
+        status = 1;
+        for (int k = 0; k < t->iters[l]; ++k) {
+            AlignDev A; tsl_align_sums s; double xi[6] = { 0, 0, 0, 0, 0, 0 };
+            int rc = align_check(m, R, T, c, depth_dev, R_out, t->stride[l], &A, who); if (rc) return rc;
+            if ((rc = align_run(m, q, A, depth_dev, acc, &s))) return rc;
+            const bool lost = s.n_used < min_used, singular = !lost && !al_solve(&s, t->damping, xi);
+            if (rep) { tsl_track_iter& it = rep->it[n]; std::memcpy(it.R, R, sizeof(R)); std::memcpy(it.T, T, sizeof(T)); std::memcpy(it.xi, xi, sizeof(xi)); it.sums = s; }
+            ++n;
+            if (lost || singular) { status = lost ? 2 : 3; failed = true; break; }
+            std::memcpy(Rl, R, sizeof(R)); std::memcpy(Tl, T, sizeof(T));
+            al_retract(xi, R, T);
+            const double n2 = ((((xi[0] * xi[0] + xi[1] * xi[1]) + xi[2] * xi[2]) + xi[3] * xi[3]) + xi[4] * xi[4]) + xi[5] * xi[5];
+            if (std::sqrt(n2) < t->min_step) { status = 0; break; }
+        }
+    }
+    std::memcpy(R_out, failed ? Rl : R, sizeof(R)); std::memcpy(T_out, failed ? Tl : T, sizeof(T));
+    if (rep) { rep->status = status; rep->iterations = n; }
+    return TSL_OK;
+}
+
+// every level is checked before anything runs
+static int track_prepare(tsl_tsdf* m, const double R0[9], const double T0[3], const tsl_align_cfg* c, const tsl_track_cfg* t, const void* depth, const void* R_out,
+                         const void* T_out, const char* who)
+{
+    TSL_REQUIRE(m, std::string(who) + ": null handle");
+    TSL_REQUIRE(R_out && T_out, std::string(who) + ": null argument");
+    int rc = track_check(t, who); if (rc) return rc;
+    AlignDev A;
+    for (int l = 0; l < t->n_levels; ++l) if ((rc = align_check(m, R0, T0, c, depth, R_out, t->stride[l], &A, who))) return rc;
+    return TSL_OK;
+}
+
+}  // namespace tsl
+
+using namespace tsl;
+
+extern "C" {
+
+int tsl_tsdf_align_linearize(tsl_tsdf* m, const double R[9], const double T[3], const tsl_align_cfg* c, const uint16_t* depth, tsl_align_sums* out)
+{
+    AlignDev A;
+    int rc = align_check(m, R, T, c, depth, out, c ? c->stride : 1, &A, "align_linearize"); if (rc) return rc;
+    TSL_HIP(hipSetDevice(m->device));
+    const hipStream_t q = ms(m);                               // issues the queued frames
+    long long* acc; const uint16_t* dd = nullptr;
+    if ((rc = align_stage(m, q, c, depth, &acc, &dd))) return rc;
+    return align_run(m, q, A, dd, acc, out);
+}
+
+int tsl_tsdf_align_linearize_dev(tsl_tsdf* m, const double R[9], const double T[3], const tsl_align_cfg* c, const void* depth_dev, void* sums_dev, void* user_stream)
+{
+    AlignDev A;
+    int rc = align_check(m, R, T, c, depth_dev, sums_dev, c ? c->stride : 1, &A, "align_linearize_dev"); if (rc) return rc;
+    TSL_HIP(hipSetDevice(m->device));
+    const hipStream_t q = ms(m);                               // behind every frame queued so far
+    if ((rc = order_before(m, (hipStream_t)user_stream, q))) return rc;
+    if ((rc = align_launch(m, q, A, (const uint16_t*)depth_dev, (long long*)sums_dev))) return rc;
+    return order_after(m, (hipStream_t)user_stream, q);
+}
+
+int tsl_align_solve(const tsl_align_sums* s, double damping, double xi[6], int32_t* singular)
+{
+    TSL_REQUIRE(s && xi && singular, "align_solve: null argument");
+    TSL_REQUIRE(std::isfinite(damping) && !(damping < 0.0), "align_solve: damping must be finite and not negative");
+    *singular = al_solve(s, damping, xi) ? 0 : 1;
+    return TSL_OK;
+}
+
+int tsl_pose_retract(const double xi[6], double R[9], double T[3])
+{
+    TSL_REQUIRE(xi && R && T, "pose_retract: null argument");
+    TSL_REQUIRE(al_finite(xi, 6) && al_finite(R, 9) && al_finite(T, 3), "pose_retract: an argument is not finite");
+    al_retract(xi, R, T);
+    return TSL_OK;
+}
+
+int tsl_tsdf_track_depth(tsl_tsdf* m, const double R0[9], const double T0[3], const tsl_align_cfg* c, const tsl_track_cfg* t, const uint16_t* depth,
+                         double R_out[9], double T_out[3], tsl_track_report* rep)
+{
+    int rc = track_prepare(m, R0, T0, c, t, depth, R_out, T_out, "track_depth"); if (rc) return rc;
+    TSL_HIP(hipSetDevice(m->device));
+    const hipStream_t q = ms(m);
+    long long* acc; const uint16_t* dd = nullptr;
+    if ((rc = align_stage(m, q, c, depth, &acc, &dd))) return rc;
+    return track_run(m, q, R0, T0, c, t, dd, acc, R_out, T_out, rep, "track_depth");
+}
+
+int tsl_tsdf_track_depth_dev(tsl_tsdf* m, const double R0[9], const double T0[3], const tsl_align_cfg* c, const tsl_track_cfg* t, const void* depth_dev,
+                             double R_out[9], double T_out[3], tsl_track_report* rep, void* user_stream)
+{
+    int rc = track_prepare(m, R0, T0, c, t, depth_dev, R_out, T_out, "track_depth_dev"); if (rc) return rc;
+    TSL_HIP(hipSetDevice(m->device));
+    const hipStream_t q = ms(m);
+    if ((rc = order_before(m, (hipStream_t)user_stream, q))) return rc;      // the image is whatever user_stream has queued for it
+    long long* acc;
+    if ((rc = align_stage(m, q, c, nullptr, &acc, nullptr))) return rc;
+    return track_run(m, q, R0, T0, c, t, (const uint16_t*)depth_dev, acc, R_out, T_out, rep, "track_depth_dev");
+}
+
+}  // extern "C"

@@ -1,4 +1,5 @@
-// tsl_interp.hpp -- the trilinear cell read shared by the ESDF point queries (tsl_esdf_query.hip) and the view renderer (tsl_render.hip): the cell of a
+// tsl_interp.hpp -- the trilinear cell read shared by the ESDF point queries (tsl_esdf_query.hip), the view renderer (tsl_render.hip) and the frame-to-model
+// alignment (tsl_align.hip): the cell of a
 // coordinate, the pool bricks of its 8 corners, and the interpolant with its gradient in ONE fixed f32 order of evaluation, which is the contract
 // tests/esdf_query_ref.py and tests/render_view_ref.py restate in numpy bit for bit (DESIGN.md sections 4.6 and 4.7).
 #pragma once
@@ -51,6 +52,23 @@ __device__ __forceinline__ void tri_grad(const float V[8], float f0, float f1, f
     *g0 = lerp_f(lerp_f(c100 - c000, c110 - c010, f1), lerp_f(c101 - c001, c111 - c011, f1), f2);
     *g1 = lerp_f(lerp_f(c010 - c000, c110 - c100, f0), lerp_f(c011 - c001, c111 - c101, f0), f2);
     *g2 = lerp_f(lerp_f(c001 - c000, c101 - c100, f0), lerp_f(c011 - c010, c111 - c110, f0), f1);
+}
+
+// the 8 corner values of the cell with base voxel (b0, b1, b2); false when a corner is outside the volume, in an unallocated brick or not observed
+__device__ __forceinline__ bool tsdf_read_cell(const MapDev& M, const int* __restrict__ T, int b0, int b1, int b2, float V[8])
+{
+    if (!(in_volume(M, b0, b1, b2) && in_volume(M, b0 + 1, b1 + 1, b2 + 1))) return false;
+    int l000; const int bb = brick_of(M, b0, b1, b2, &l000);
+    const int li = l000 >> 8, lj = (l000 >> 4) & 15, lk = l000 & 15;
+    int P[8]; cell_bricks(M, T, bb, li, lj, lk, P);
+    // all 16 gathers are issued before any is used: two dependent latencies per sample (table, then data)
+    uint32_t tw[8]; int ob[8];
+#pragma unroll
+    for (int c = 0; c < 8; ++c) { const size_t v = corner_voxel(P, c, li, lj, lk); tw[c] = M.tw[v]; ob[c] = M.obs[v]; }
+    bool known = true;
+#pragma unroll
+    for (int c = 0; c < 8; ++c) { known = known && P[c] >= 0 && ob[c] > 0; V[c] = h2f((h16)(tw[c] & 0xffffu)); }
+    return known;
 }
 
 }  // namespace tsl

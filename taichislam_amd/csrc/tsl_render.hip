@@ -38,23 +38,6 @@ struct ViewDev {
     int h, w, S, flags;
 };
 
-// the 8 corner values of the cell with base voxel (b0, b1, b2); false when a corner is outside the volume, in an unallocated brick or not observed
-__device__ __forceinline__ bool rv_read_cell(const MapDev& M, const int* __restrict__ T, int b0, int b1, int b2, float V[8])
-{
-    if (!(in_volume(M, b0, b1, b2) && in_volume(M, b0 + 1, b1 + 1, b2 + 1))) return false;
-    int l000; const int bb = brick_of(M, b0, b1, b2, &l000);
-    const int li = l000 >> 8, lj = (l000 >> 4) & 15, lk = l000 & 15;
-    int P[8]; cell_bricks(M, T, bb, li, lj, lk, P);
-    // all 16 gathers are issued before any is used: two dependent latencies per sample (table, then data)
-    uint32_t tw[8]; int ob[8];
-#pragma unroll
-    for (int c = 0; c < 8; ++c) { const size_t v = corner_voxel(P, c, li, lj, lk); tw[c] = M.tw[v]; ob[c] = M.obs[v]; }
-    bool known = true;
-#pragma unroll
-    for (int c = 0; c < 8; ++c) { known = known && P[c] >= 0 && ob[c] > 0; V[c] = h2f((h16)(tw[c] & 0xffffu)); }
-    return known;
-}
-
 // sample m of the ray: position and base voxel, with the arithmetic of the walk; false when a coordinate is not finite
 __device__ __forceinline__ bool rv_sample_pos(const ViewDev& W, const float d[3], int m, float* t, float p[3], float u[3], int b[3])
 {
@@ -132,7 +115,7 @@ __global__ void __launch_bounds__(256, 5) k_render_view(MapDev M, int s, ViewDev
             if (in_volume(M, b[0], b[1], b[2])) {
                 int l; const int P0 = T[brick_of(M, b[0], b[1], b[2], &l)];
                 if (P0 >= 0) {
-                    kn = rv_read_cell(M, T, b[0], b[1], b[2], V);
+                    kn = tsdf_read_cell(M, T, b[0], b[1], b[2], V);
                     if (kn) sv = tri_value(V, u[0] - (float)b[0], u[1] - (float)b[1], u[2] - (float)b[2]);
                 } else if (skip) next = rv_skip_brick(M, W, d, n, b);
             } else if (skip) next = rv_skip_outside(M, W, d, n, b);
@@ -150,7 +133,7 @@ __global__ void __launch_bounds__(256, 5) k_render_view(MapDev M, int s, ViewDev
 #pragma unroll
         for (int a = 0; a < 3; ++a) { p[a] = W.T[a] + ts * d[a]; u[a] = p[a] / W.vs; b[a] = cell_floor(u[a]); }
         const bool fin = isfinite(p[0]) && isfinite(p[1]) && isfinite(p[2]);
-        bool ok = fin && rv_read_cell(M, T, b[0], b[1], b[2], V);
+        bool ok = fin && tsdf_read_cell(M, T, b[0], b[1], b[2], V);
         if (ok) {
             tri_grad(V, u[0] - (float)b[0], u[1] - (float)b[1], u[2] - (float)b[2], &g0, &g1, &g2);
             const float len = sqrtf((g0 * g0 + g1 * g1) + g2 * g2);

@@ -84,6 +84,52 @@ def depth_to_mm(depth):
     return np.clip(np.rint(np.float32(1000.0) * d), 0, 65535).astype(np.uint16)
 
 
+def align_config(K=None, shape=(480, 640), stride=1, d_min=None, d_max=None, r_max=None, g_max=None, huber=0.0, counts_only=False):
+    """The tsl_align_cfg of DenseTSDF.align_linearize / track_depth; None = the map's default (passed as 0).  The library checks the values."""
+    cfg = _lib.AlignCfg()
+    if K is not None:
+        k = np.asarray(K, dtype=np.float64).reshape(-1)
+        if k.size != 9:
+            raise ValueError("align: K must hold 9 values")
+        cfg.K[:] = k.tolist()
+    cfg.h, cfg.w, cfg.stride = int(shape[0]), int(shape[1]), int(stride)
+    for name, v in (("d_min", d_min), ("d_max", d_max), ("r_max", r_max), ("g_max", g_max), ("huber", huber)):
+        if v is not None:
+            setattr(cfg, name, float(v))
+    cfg.flags = 1 if counts_only else 0
+    return cfg
+
+
+ALIGN_SCALE = 2.0 ** -20       # the sums of tsl_align_sums are 2^-20 fixed point
+
+
+def align_sums_dict(v):
+    """The 33 integers of tsl_align_sums (H[21] upper triangle row-major, b[6], e, five counts) as the dict align_linearize returns."""
+    v = np.asarray(v, dtype=np.int64).reshape(-1)[:33]
+    H = np.zeros((6, 6), np.int64)
+    iu = np.triu_indices(6)
+    H[iu] = v[:21]
+    H[(iu[1], iu[0])] = v[:21]
+    out = {"H": H, "b": v[21:27].copy(), "e": int(v[27]), "H_f": H.astype(np.float64) * ALIGN_SCALE, "b_f": v[21:27].astype(np.float64) * ALIGN_SCALE,
+           "e_f": float(v[27]) * ALIGN_SCALE, "sums": v.copy()}
+    for i, n in enumerate(("n_used", "n_gate", "n_unknown", "n_far", "n_grad")):
+        out[n] = int(v[28 + i])
+    return out
+
+
+def _depth_image(depth):
+    """(pointer, (h, w), keep-alive, is_device) of a uint16 millimetre image: a numpy array or a torch CUDA tensor, the forms recast_depth_to_map accepts"""
+    if _is_device_tensor(depth):
+        torch = _torch()
+        assert depth.dim() == 2 and depth.is_contiguous() and depth.dtype in _DEPTH_DTYPES(torch), \
+            "device depth must be a contiguous [h,w] uint16 tensor of millimetres (int16 = the same bits)"
+        return C.c_void_p(depth.data_ptr()), (int(depth.shape[0]), int(depth.shape[1])), depth, True
+    d = np.ascontiguousarray(np.asarray(depth, dtype=np.uint16))
+    if d.ndim != 2:
+        raise ValueError("depth must be a 2-d uint16 array")
+    return _vp(d), d.shape, d, False
+
+
 class DenseTSDF(BaseMap):
     _prefix = "tsl_tsdf"
 
@@ -619,6 +665,69 @@ class DenseTSDF(BaseMap):
         status = np.empty((h, w), np.uint8)
         _lib.check(self.L.tsl_tsdf_render_view(self.h, r, t, C.byref(cfg), _vp(depth), _vp(normal), _vp(rgb), _vp(status)))
         return depth, normal, rgb, status
+
+    # ---- frame-to-model alignment (tsl_align.hip) ---------------------------------------------------
+    def align_linearize(self, depth, R, T, K=None, stride=1, d_min=None, d_max=None, r_max=None, g_max=None, huber=0.0, device=False, counts_only=False):
+        """The normal equations of aligning a depth image (uint16 millimetres [h, w]) to the TSDF at the camera-to-map pose (R, T) -- in the frame of
+        render_view: Gauss-Newton on s(R p + T), s the trilinear interpolant of the TSDF, over every stride-th pixel of every stride-th row.  Returns a
+        dict: H (6 x 6 int64, symmetric), b (6), e -- the sums of J J^T, J s and s^2 in 2^-20 fixed point, J = (grad s, p x grad s) -- the same as
+        float64 (H_f, b_f, e_f), the 33 integers as the library orders them (sums) and the counts n_used, n_gate (no depth or outside d_min .. d_max),
+        n_unknown (the point touches unobserved voxels), n_far (|s| > r_max), n_grad (gradient 0 or longer than g_max).  The integers do not depend on the
+        schedule.  None = the map's default: its depth intrinsics, min / max_ray_length, r_max = internal_voxels * voxel, g_max = 4; huber = 0 is off.
+        device=True takes a torch CUDA tensor and returns an int64 tensor of 40 on the device (the 33 integers, then zeros), asynchronously, ordered
+        with torch.cuda.current_stream (tsl_tsdf_align_linearize_dev).  counts_only=True leaves H, b and e at 0 and only sorts the pixels into the buckets
+        (the A/B switch of tools/bench_track.py: what the gathers cost without the sums)."""
+        ptr, shape, keep, on_dev = _depth_image(depth)
+        cfg = align_config(K, shape, stride, d_min, d_max, r_max, g_max, huber, counts_only)
+        r, t = _dptr(R, 9)[1], _dptr(T, 3)[1]
+        if device:
+            if not on_dev:
+                raise ValueError("align_linearize: device=True takes a torch CUDA tensor")
+            torch = _torch()
+            dev = torch.device(f"cuda:{self.device}")
+            out = torch.empty(40, dtype=torch.int64, device=dev)
+            _lib.check(self.L.tsl_tsdf_align_linearize_dev(self.h, r, t, C.byref(cfg), ptr, out.data_ptr(), torch.cuda.current_stream(dev).cuda_stream))
+            return out
+        if on_dev:
+            keep = keep.cpu().numpy().view(np.uint16)
+            ptr = _vp(keep)
+        sums = _lib.AlignSums()
+        _lib.check(self.L.tsl_tsdf_align_linearize(self.h, r, t, C.byref(cfg), ptr, C.byref(sums)))
+        return align_sums_dict(np.frombuffer(sums, dtype=np.int64))
+
+    def track_depth(self, depth, R, T, K=None, levels=((8, 4), (4, 4), (2, 6)), min_step=1e-4, damping=0.0, min_used=None, **gates):
+        """Refine the camera-to-map pose (R, T) of a depth image against the TSDF: up to 4 levels (stride, iterations) of Gauss-Newton steps on the normal
+        equations of align_linearize, solved on the host in float64 (Cholesky) and applied through the Cayley map.  A level ends early when the step
+        sqrt(|v|^2 + |omega|^2) falls below min_step.  Returns (R 3 x 3, T 3, info); info["status"]: 0 the last level ended by the threshold, 1 its
+        iterations were exhausted, 2 lost (a linearisation used fewer than min_used pixels; default 6), 3 singular -- for 2 and 3 the pose returned is
+        the last one that gave a step, or the guess.  info["iterations"] counts the linearisations, info["records"] holds for each the pose it was made
+        at (R, T), the step xi = (v, omega) and the dict of align_linearize.  depth: a numpy array or a torch CUDA tensor (ordered with
+        torch.cuda.current_stream); gates: the d_min / d_max / r_max / g_max / huber of align_linearize."""
+        ptr, shape, keep, on_dev = _depth_image(depth)
+        cfg = align_config(K, shape, 1, **gates)
+        levels = [(int(a), int(b)) for a, b in levels]
+        tc = _lib.TrackCfg()
+        tc.n_levels = len(levels)
+        for i, (st, it) in enumerate(levels[:4]):
+            tc.stride[i], tc.iters[i] = st, it
+        tc.min_used, tc.min_step, tc.damping = (0 if min_used is None else int(min_used)), float(min_step), float(damping)
+        r, t = _dptr(R, 9)[1], _dptr(T, 3)[1]
+        Ro, To = np.empty(9, np.float64), np.empty(3, np.float64)
+        rep = _lib.TrackReport()
+        ro, to = Ro.ctypes.data_as(_lib.dp), To.ctypes.data_as(_lib.dp)
+        if on_dev:
+            torch = _torch()
+            _lib.check(self.L.tsl_tsdf_track_depth_dev(self.h, r, t, C.byref(cfg), C.byref(tc), ptr, ro, to, C.byref(rep),
+                                                       torch.cuda.current_stream(keep.device).cuda_stream))
+        else:
+            _lib.check(self.L.tsl_tsdf_track_depth(self.h, r, t, C.byref(cfg), C.byref(tc), ptr, ro, to, C.byref(rep)))
+        records = []
+        for i in range(rep.iterations):
+            it = rep.it[i]
+            rec = align_sums_dict(np.frombuffer(it.sums, dtype=np.int64))
+            rec.update(R=np.array(it.R[:], np.float64).reshape(3, 3), T=np.array(it.T[:], np.float64), xi=np.array(it.xi[:], np.float64))
+            records.append(rec)
+        return Ro.reshape(3, 3), To, {"status": int(rep.status), "iterations": int(rep.iterations), "records": records}
 
     # ---- ESDF (definition from the legacy dense_esdf.py:228-333; see DESIGN.md) -----------------------------------
     def update_esdf(self, gamma=None, max_dist=None, wait=True):
