@@ -64,7 +64,7 @@ typedef struct {
 
 /* kernel ids for tsl_tsdf_prof_query */
 enum { TSL_K_VOXELIZE = 0, TSL_K_SORT = 1, TSL_K_RAYS = 2, TSL_K_INTEGRATE = 3, TSL_K_FINALIZE = 4,
-       TSL_K_MESH = 5, TSL_K_SEGMENTS = 6, TSL_K_BIN = 7, TSL_K_ESDF = 8, TSL_K_FUSE = 9, TSL_K_COUNT };
+       TSL_K_MESH = 5, TSL_K_SEGMENTS = 6, TSL_K_BIN = 7, TSL_K_ESDF = 8, TSL_K_FUSE = 9, TSL_K_REGISTER = 10, TSL_K_COUNT };
 
 const char* tsl_version(void);
 const char* tsl_last_error(void);
@@ -353,6 +353,45 @@ int  tsl_tsdf_track_depth(tsl_tsdf* m, const double R0[9], const double T0[3], c
                           double R_out[9], double T_out[3], tsl_track_report* rep);
 int  tsl_tsdf_track_depth_dev(tsl_tsdf* m, const double R0[9], const double T0[3], const tsl_align_cfg* c, const tsl_track_cfg* t, const void* depth_dev,
                               double R_out[9], double T_out[3], tsl_track_report* rep, void* user_stream);
+
+/* ---- map-to-map registration (tsl_register.hip): a TSDF submap against another map, Gauss-Newton on the difference of the two signed distances --
+ * minimise the sum of (s(R q_i + T) - t_i)^2 over X = (R, T), q_i the voxels of the source submap near its surface, t_i the values it stores there and
+ * s the trilinear interpolant of the destination.  It tells whether two submaps agree where they overlap, returns the relative pose at which they
+ * do, and the normal equations behind it: a constraint for a pose graph.  The reference takes its submap poses from a pose graph outside and has no
+ * counterpart.  dst / dst_sid: the destination map and submap; -1 = the frame of tsl_tsdf_query_points (the active submap; submap 0 on a global
+ * map).  src / src_sid: the source map and submap; -1 = its active submap.  src and dst may be the same handle; they must live on the same device
+ * and have bit-equal f32 voxel sizes (the assumption of tsl_tsdf_fuse_submaps).  R (row-major) / T take source-submap coordinates to destination
+ * coordinates, given as doubles and rounded to f32 once.
+ * Definition (all f32, no contraction, in this order).  Visited: the observed voxels of the source submap whose indices (i, j, k)
+ * are each divisible by stride; unobserved voxels are neither visited nor counted.  Each visited voxel lands in exactly one bucket, tested in this order:
+ *   n_gate     w = f16 weight fails w >= w_min, or fabsf(t) > band, t the stored f16 TSDF value.  Otherwise q = ((float)i * voxel, (float)j * voxel,
+ *              (float)k * voxel) and p[a] = ((R[a][0] * q0 + R[a][1] * q1) + R[a][2] * q2) + T[a]
+ *   n_unknown  the sample of dst at p is not KNOWN in the sense of tsl_tsdf_render_view (8 corners in the volume, in allocated bricks of dst_sid and
+ *              observed, p finite).  Otherwise s = the trilinear interpolant, g = its gradient per metre (tsl_esdf_query_points mode 1)
+ *   n_far      |s| > r_max
+ *   n_grad     gg = (g0 * g0 + g1 * g1) + g2 * g2 is 0 or > g_max * g_max
+ *   n_used     r = s - t, c = p x g, J = (g0, g1, g2, c0, c1, c2), wgt = huber > 0 && |r| > huber ? huber / |r| : 1, wJ[a] = wgt * J[a]; the 28 products
+ *              H_ab = wJ[a] * J[b] (a <= b, row-major upper triangle), b_a = wJ[a] * r, e = (wgt * r) * r
+ * Every product x is added as the integer rint(x * 2^20) into an int64 sum; the result is a tsl_align_sums, the same 33 integers in the same order,
+ * so tsl_align_solve and tsl_pose_retract serve unchanged (the step is the left twist p <- p + v + omega x p).
+ * tsl_register_cfg: stride 1, 2, 4, 8 or 16; w_min (0 = every weight passes); band (0 = 2 * voxel); r_max (0 = internal_voxels * voxel of dst); g_max
+ * (0 = 4); huber (0 = off); flags bit 0 = counts only: the products and their reduction are left out, H, b and e are 0 (the A/B switch of
+ * tools/bench_register.py).  The call is refused unless M^2 * 2^20 * V <= 2^62, M = max(2 L g_max, g_max, r_max + band), L the largest absolute
+ * coordinate of dst's volume, V = min(max_bricks, bricks per submap) of src * (16 / stride)^3, an upper bound of the visited voxels: no sum can overflow.
+ * tsl_tsdf_register_submap iterates linearise, solve, retract as tsl_tsdf_track_depth does, with the same tsl_track_cfg (every level's stride one of
+ * 1, 2, 4, 8, 16; the Python default is (4, 4 iterations), (2, 4), (1, 6)) and the same tsl_track_report: min_used, min_step, damping, the four
+ * statuses and the pose returned on lost / singular are those of tsl_tsdf_track_depth.
+ * Both are host forms: they issue the queued frames of both handles, wait for the source's work (as tsl_tsdf_fuse_submaps does), run on dst's stream
+ * and wait.  Neither writes to either map.  dst's export staging buffer holds the accumulator: device pointers from tsl_esdf_export_dev are invalid
+ * afterwards.  With profiling on, tsl_tsdf_prof_query(dst, TSL_K_REGISTER) returns the time of the kernel alone.
+ * TSL_ERR_ARG (the text names the entry point): a null handle / pose / cfg / out, a non-finite pose or parameter, a stride that is not a power of two
+ * in 1 .. 16, a negative w_min / band / r_max / g_max / huber / damping / min_step, a submap id outside -1 .. max_submap_num - 1 (outside -1 .. 0 on a
+ * global map), maps on different devices or with different voxel sizes, the overflow bound, more than 4 levels or 64 iterations. */
+typedef struct { int32_t stride; float w_min, band, r_max, g_max, huber; int32_t flags; } tsl_register_cfg;
+int  tsl_tsdf_register_linearize(tsl_tsdf* dst, int dst_sid, tsl_tsdf* src, int src_sid, const double R[9], const double T[3],
+                                 const tsl_register_cfg* c, tsl_align_sums* out);
+int  tsl_tsdf_register_submap(tsl_tsdf* dst, int dst_sid, tsl_tsdf* src, int src_sid, const double R0[9], const double T0[3],
+                              const tsl_register_cfg* c, const tsl_track_cfg* t, double R_out[9], double T_out[3], tsl_track_report* rep);
 
 /* backend knobs for A/B-ing kernel variants: name in
      "variant"  0|1: one global int64 atomic pair per ray step, 2 (default): brick-binned LDS accumulation

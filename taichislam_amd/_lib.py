@@ -6,9 +6,9 @@ import os
 from . import build as _build
 
 TSL_OK = 0
-K_VOXELIZE, K_SORT, K_RAYS, K_INTEGRATE, K_FINALIZE, K_MESH, K_SEGMENTS, K_BIN, K_ESDF, K_FUSE = range(10)
+K_VOXELIZE, K_SORT, K_RAYS, K_INTEGRATE, K_FINALIZE, K_MESH, K_SEGMENTS, K_BIN, K_ESDF, K_FUSE, K_REGISTER = range(11)
 KERNEL_NAMES = {K_VOXELIZE: "voxelize", K_SORT: "sort", K_RAYS: "build_rays", K_INTEGRATE: "integrate",
-                K_FINALIZE: "finalize", K_MESH: "marching_cubes", K_SEGMENTS: "segments", K_BIN: "bin", K_ESDF: "esdf", K_FUSE: "fuse"}
+                K_FINALIZE: "finalize", K_MESH: "marching_cubes", K_SEGMENTS: "segments", K_BIN: "bin", K_ESDF: "esdf", K_FUSE: "fuse", K_REGISTER: "register"}
 
 
 class TsdfCfg(C.Structure):
@@ -67,6 +67,12 @@ class AlignCfg(C.Structure):
 class AlignSums(C.Structure):
     """tsl_align_sums: the normal equations in 2^-20 fixed point and the five pixel counts, 33 x int64"""
     _fields_ = [("H", C.c_int64 * 21), ("b", C.c_int64 * 6)] + [(n, C.c_int64) for n in ("e", "n_used", "n_gate", "n_unknown", "n_far", "n_grad")]
+
+
+class RegisterCfg(C.Structure):
+    """tsl_register_cfg (tsl_tsdf_register_linearize, tsl_tsdf_register_submap): a zero band / r_max / g_max means the default, w_min 0 = every weight, huber 0 = off"""
+    _fields_ = [("stride", C.c_int32), ("w_min", C.c_float), ("band", C.c_float), ("r_max", C.c_float), ("g_max", C.c_float), ("huber", C.c_float),
+                ("flags", C.c_int32)]
 
 
 class TrackCfg(C.Structure):
@@ -171,6 +177,8 @@ SIGNATURES = {
     "tsl_pose_retract": (C.c_int, [dp, dp, dp]),
     "tsl_tsdf_track_depth": (C.c_int, [vp, dp, dp, C.POINTER(AlignCfg), C.POINTER(TrackCfg), vp, dp, dp, C.POINTER(TrackReport)]),
     "tsl_tsdf_track_depth_dev": (C.c_int, [vp, dp, dp, C.POINTER(AlignCfg), C.POINTER(TrackCfg), vp, dp, dp, C.POINTER(TrackReport), vp]),
+    "tsl_tsdf_register_linearize": (C.c_int, [vp, C.c_int, vp, C.c_int, dp, dp, C.POINTER(RegisterCfg), C.POINTER(AlignSums)]),
+    "tsl_tsdf_register_submap": (C.c_int, [vp, C.c_int, vp, C.c_int, dp, dp, C.POINTER(RegisterCfg), C.POINTER(TrackCfg), dp, dp, C.POINTER(TrackReport)]),
     "tsl_tsdf_set_option": (C.c_int, [vp, C.c_char_p, C.c_int]),
     "tsl_tsdf_get_option": (C.c_int, [vp, C.c_char_p, C.POINTER(C.c_int)]),
     "tsl_tsdf_prof_enable": (C.c_int, [vp, C.c_int]),

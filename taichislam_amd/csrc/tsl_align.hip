@@ -22,17 +22,9 @@
 // usual): what the gathers cost alone (tools/bench_track.py).
 #include <cmath>
 #include "tsl_interp.hpp"
+#include "tsl_align_common.hpp"      // al_fix, al_halve, the step, the retraction and the iteration: shared with tsl_register.hip
 
 namespace tsl {
-
-#define AL_SLOTS 40                    // int64 slots of the device accumulator: 33 used (tsl_align_sums), the rest stay 0
-#define AL_NPROD 28
-#define AL_SCALE 1048576.0f            // 2^20
-#define AL_USED 0
-#define AL_GATE 1
-#define AL_UNKNOWN 2
-#define AL_FAR 3
-#define AL_GRAD 4
 
 struct AlignDev {
     float R[9], T[3];                  // camera-to-map pose in the frame of the point queries, rounded to f32 once
@@ -42,27 +34,6 @@ struct AlignDev {
     int h, w, stride, hh, ww;          // image size; visited rows / columns
     int flags;                         // bit 0: counts only
 };
-
-// rint(x * 2^20) as an integer.  The product is exact in f32 (a power of two; the overflow refusal keeps it far below 2^63), so this is
-// (int64) rint((double)x * 2^20).
-__device__ __forceinline__ long long al_fix(float x)
-{
-    const float q = rintf(x * AL_SCALE);
-    if (fabsf(q) < 2147483648.0f) return (long long)(int)q;
-    return (long long)q;
-}
-
-// one halving step of the wave reduction: v[0 .. N-1] of this lane and of lane ^ D become v[0 .. N/2-1], the sums of the half this lane keeps
-template <int N, int D>
-__device__ __forceinline__ void al_halve(long long (&v)[32], int lane)
-{
-    const bool up = (lane & D) != 0;
-#pragma unroll
-    for (int i = 0; i < N / 2; ++i) {
-        const long long keep = up ? v[i + N / 2] : v[i], send = up ? v[i] : v[i + N / 2];
-        v[i] = keep + __shfl_xor(send, D);
-    }
-}
 
 __global__ void __launch_bounds__(256) k_align_linearize(MapDev M, int s, AlignDev A, const uint16_t* __restrict__ depth, long long* __restrict__ acc)
 {
@@ -139,8 +110,6 @@ __global__ void __launch_bounds__(256) k_align_linearize(MapDev M, int s, AlignD
     }
 }
 
-static bool al_finite(const double* a, int n) { for (int i = 0; i < n; ++i) if (!std::isfinite(a[i])) return false; return true; }
-
 // the checks and defaults every form shares; `stride` replaces the configuration's (the levels of the tracker)
 static int align_check(tsl_tsdf* m, const double R[9], const double T[3], const tsl_align_cfg* c, const void* depth, const void* out, int stride,
                        AlignDev* A, const char* who)
@@ -191,8 +160,6 @@ static int align_launch(tsl_tsdf* m, hipStream_t q, const AlignDev& A, const uin
     return TSL_OK;
 }
 
-static long long* al_pinned(tsl_tsdf* m) { return reinterpret_cast<long long*>(m->h_ints + 128); }      // the upper part of the pinned scratch: 40 x int64
-
 // one linearisation on q with the result on the host: launch, copy back through the pinned buffer, wait
 static int align_run(tsl_tsdf* m, hipStream_t q, const AlignDev& A, const uint16_t* depth_dev, long long* acc, tsl_align_sums* out)
 {
@@ -216,109 +183,15 @@ static int align_stage(tsl_tsdf* m, hipStream_t q, const tsl_align_cfg* c, const
     return TSL_OK;
 }
 
-// ---- the step and the retraction: host code, float64, in this order (tests/track_ref.py restates both) ----
-
-static void al_system(const tsl_align_sums* s, double damping, double Hm[6][6], double b[6])
-{
-    int k = 0;
-    for (int a = 0; a < 6; ++a) for (int c = a; c < 6; ++c) { const double x = (double)s->H[k++] * (1.0 / 1048576.0); Hm[a][c] = x; Hm[c][a] = x; }
-    for (int a = 0; a < 6; ++a) { b[a] = (double)s->b[a] * (1.0 / 1048576.0); Hm[a][a] += damping * Hm[a][a]; }
-}
-
-// xi = -H^-1 b by Cholesky L L^T without pivoting, column by column; false (xi = 0) when a pivot is <= 0 or not finite
-static bool al_solve(const tsl_align_sums* s, double damping, double xi[6])
-{
-    double Hm[6][6], b[6], Lm[6][6], y[6];
-    al_system(s, damping, Hm, b);
-    for (int a = 0; a < 6; ++a) xi[a] = 0.0;
-    for (int j = 0; j < 6; ++j) {
-        double d = Hm[j][j];
-        for (int k = 0; k < j; ++k) d -= Lm[j][k] * Lm[j][k];
-        if (!(d > 0.0) || !std::isfinite(d)) return false;
-        Lm[j][j] = std::sqrt(d);
-        for (int i = j + 1; i < 6; ++i) {
-            double t = Hm[i][j];
-            for (int k = 0; k < j; ++k) t -= Lm[i][k] * Lm[j][k];
-            Lm[i][j] = t / Lm[j][j];
-        }
-    }
-    for (int i = 0; i < 6; ++i) {                                  // L y = -b
-        double t = -b[i];
-        for (int k = 0; k < i; ++k) t -= Lm[i][k] * y[k];
-        y[i] = t / Lm[i][i];
-    }
-    double x[6];
-    for (int i = 5; i >= 0; --i) {                                 // L^T x = y
-        double t = y[i];
-        for (int k = i + 1; k < 6; ++k) t -= Lm[k][i] * x[k];
-        x[i] = t / Lm[i][i];
-    }
-    for (int a = 0; a < 6; ++a) if (!std::isfinite(x[a])) return false;
-    for (int a = 0; a < 6; ++a) xi[a] = x[a];
-    return true;
-}
-
-// the Cayley map of omega = xi[3..5]: R <- C R, T <- C T + v
-static void al_retract(const double xi[6], double R[9], double T[3])
-{
-    const double a[3] = { xi[3] * 0.5, xi[4] * 0.5, xi[5] * 0.5 };
-    const double aa = (a[0] * a[0] + a[1] * a[1]) + a[2] * a[2], den = 1.0 + aa;
-    const double S[3][3] = { { 0.0, -a[2], a[1] }, { a[2], 0.0, -a[0] }, { -a[1], a[0], 0.0 } };
-    double Cm[3][3], Rn[9], Tn[3];
-    for (int i = 0; i < 3; ++i) for (int j = 0; j < 3; ++j) Cm[i][j] = (((i == j ? 1.0 - aa : 0.0) + (2.0 * a[i]) * a[j]) + 2.0 * S[i][j]) / den;
-    for (int i = 0; i < 3; ++i) {
-        for (int j = 0; j < 3; ++j) Rn[i * 3 + j] = (Cm[i][0] * R[j] + Cm[i][1] * R[3 + j]) + Cm[i][2] * R[6 + j];
-        Tn[i] = ((Cm[i][0] * T[0] + Cm[i][1] * T[1]) + Cm[i][2] * T[2]) + xi[i];
-    }
-    for (int i = 0; i < 9; ++i) R[i] = Rn[i];
-    for (int i = 0; i < 3; ++i) T[i] = Tn[i];
-}
-
-static int track_check(const tsl_track_cfg* t, const char* who)
-{
-    const std::string w(who);
-    TSL_REQUIRE(t, w + ": null argument");
-    TSL_REQUIRE(t->n_levels >= 1 && t->n_levels <= 4, w + ": 1 .. 4 levels");
-    int total = 0;
-    for (int l = 0; l < t->n_levels; ++l) {
-        TSL_REQUIRE(t->stride[l] >= 1, w + ": stride must be at least 1");
-        TSL_REQUIRE(t->iters[l] >= 0 && t->iters[l] <= 64, w + ": at most 64 iterations");
-        total += t->iters[l];
-    }
-    TSL_REQUIRE(total <= 64, w + ": at most 64 iterations");
-    TSL_REQUIRE(t->min_used >= 0, w + ": min_used must not be negative");
-    TSL_REQUIRE(std::isfinite(t->min_step) && std::isfinite(t->damping) && !(t->min_step < 0.0) && !(t->damping < 0.0), w + ": min_step and damping must be finite and not negative");
-    return TSL_OK;
-}
-
-// the iteration; the depth image is on the device, q has been ordered behind whatever produced it
+// the iteration (al_iterate); the depth image is on the device, q has been ordered behind whatever produced it
 static int track_run(tsl_tsdf* m, hipStream_t q, const double R0[9], const double T0[3], const tsl_align_cfg* c, const tsl_track_cfg* t, const uint16_t* depth_dev,
                      long long* acc, double R_out[9], double T_out[3], tsl_track_report* rep, const char* who)
 {
-    double R[9], T[3], Rl[9], Tl[3];                               // the current pose; the last one that gave a step
-    std::memcpy(R, R0, sizeof(R)); std::memcpy(T, T0, sizeof(T)); std::memcpy(Rl, R0, sizeof(Rl)); std::memcpy(Tl, T0, sizeof(Tl));
-    const int64_t min_used = t->min_used > 0 ? t->min_used : 6;
-    int n = 0, status = 1;
-    bool failed = false;
-    for (int l = 0; l < t->n_levels && !failed; ++l) {
-        status = 1;
-        for (int k = 0; k < t->iters[l]; ++k) {
-            AlignDev A; tsl_align_sums s; double xi[6] = { 0, 0, 0, 0, 0, 0 };
-            int rc = align_check(m, R, T, c, depth_dev, R_out, t->stride[l], &A, who); if (rc) return rc;
-            if ((rc = align_run(m, q, A, depth_dev, acc, &s))) return rc;
-            const bool lost = s.n_used < min_used, singular = !lost && !al_solve(&s, t->damping, xi);
-            if (rep) { tsl_track_iter& it = rep->it[n]; std::memcpy(it.R, R, sizeof(R)); std::memcpy(it.T, T, sizeof(T)); std::memcpy(it.xi, xi, sizeof(xi)); it.sums = s; }
-            ++n;
-            if (lost || singular) { status = lost ? 2 : 3; failed = true; break; }
-            std::memcpy(Rl, R, sizeof(R)); std::memcpy(Tl, T, sizeof(T));
-            al_retract(xi, R, T);
-            const double n2 = ((((xi[0] * xi[0] + xi[1] * xi[1]) + xi[2] * xi[2]) + xi[3] * xi[3]) + xi[4] * xi[4]) + xi[5] * xi[5];
-            if (std::sqrt(n2) < t->min_step) { status = 0; break; }
-        }
-    }
-    std::memcpy(R_out, failed ? Rl : R, sizeof(R)); std::memcpy(T_out, failed ? Tl : T, sizeof(T));
-    if (rep) { rep->status = status; rep->iterations = n; }
-    return TSL_OK;
+    return al_iterate(R0, T0, t, [&](int stride, const double* R, const double* T, tsl_align_sums* s) {
+        AlignDev A;
+        const int rc = align_check(m, R, T, c, depth_dev, R_out, stride, &A, who); if (rc) return rc;
+        return align_run(m, q, A, depth_dev, acc, s);
+    }, R_out, T_out, rep);
 }
 
 // every level is checked before anything runs

@@ -117,6 +117,40 @@ def align_sums_dict(v):
     return out
 
 
+REGISTER_LEVELS = ((4, 4), (2, 4), (1, 6))       # (stride, iterations) of DenseTSDF.register_submap
+
+
+def register_config(stride=1, w_min=0, band=0, r_max=0, g_max=0, huber=0, counts_only=False):
+    """The tsl_register_cfg of DenseTSDF.register_linearize / register_submap; 0 = the default.  The library checks the values."""
+    cfg = _lib.RegisterCfg()
+    cfg.stride = int(stride)
+    cfg.w_min, cfg.band, cfg.r_max, cfg.g_max, cfg.huber = float(w_min), float(band), float(r_max), float(g_max), float(huber)
+    cfg.flags = 1 if counts_only else 0
+    return cfg
+
+
+def _track_config(levels, min_step, damping, min_used):
+    """The tsl_track_cfg of track_depth / register_submap; the library checks the values (a fifth level is counted, not stored)."""
+    levels = [(int(a), int(b)) for a, b in levels]
+    tc = _lib.TrackCfg()
+    tc.n_levels = len(levels)
+    for i, (st, it) in enumerate(levels[:4]):
+        tc.stride[i], tc.iters[i] = st, it
+    tc.min_used, tc.min_step, tc.damping = (0 if min_used is None else int(min_used)), float(min_step), float(damping)
+    return tc
+
+
+def _track_info(rep):
+    """The info dict of track_depth / register_submap from a tsl_track_report"""
+    records = []
+    for i in range(rep.iterations):
+        it = rep.it[i]
+        rec = align_sums_dict(np.frombuffer(it.sums, dtype=np.int64))
+        rec.update(R=np.array(it.R[:], np.float64).reshape(3, 3), T=np.array(it.T[:], np.float64), xi=np.array(it.xi[:], np.float64))
+        records.append(rec)
+    return {"status": int(rep.status), "iterations": int(rep.iterations), "records": records}
+
+
 def _depth_image(depth):
     """(pointer, (h, w), keep-alive, is_device) of a uint16 millimetre image: a numpy array or a torch CUDA tensor, the forms recast_depth_to_map accepts"""
     if _is_device_tensor(depth):
@@ -705,12 +739,7 @@ class DenseTSDF(BaseMap):
         torch.cuda.current_stream); gates: the d_min / d_max / r_max / g_max / huber of align_linearize."""
         ptr, shape, keep, on_dev = _depth_image(depth)
         cfg = align_config(K, shape, 1, **gates)
-        levels = [(int(a), int(b)) for a, b in levels]
-        tc = _lib.TrackCfg()
-        tc.n_levels = len(levels)
-        for i, (st, it) in enumerate(levels[:4]):
-            tc.stride[i], tc.iters[i] = st, it
-        tc.min_used, tc.min_step, tc.damping = (0 if min_used is None else int(min_used)), float(min_step), float(damping)
+        tc = _track_config(levels, min_step, damping, min_used)
         r, t = _dptr(R, 9)[1], _dptr(T, 3)[1]
         Ro, To = np.empty(9, np.float64), np.empty(3, np.float64)
         rep = _lib.TrackReport()
@@ -721,13 +750,40 @@ class DenseTSDF(BaseMap):
                                                        torch.cuda.current_stream(keep.device).cuda_stream))
         else:
             _lib.check(self.L.tsl_tsdf_track_depth(self.h, r, t, C.byref(cfg), C.byref(tc), ptr, ro, to, C.byref(rep)))
-        records = []
-        for i in range(rep.iterations):
-            it = rep.it[i]
-            rec = align_sums_dict(np.frombuffer(it.sums, dtype=np.int64))
-            rec.update(R=np.array(it.R[:], np.float64).reshape(3, 3), T=np.array(it.T[:], np.float64), xi=np.array(it.xi[:], np.float64))
-            records.append(rec)
-        return Ro.reshape(3, 3), To, {"status": int(rep.status), "iterations": int(rep.iterations), "records": records}
+        return Ro.reshape(3, 3), To, _track_info(rep)
+
+    # ---- map-to-map registration (tsl_register.hip) -------------------------------------------------
+    def register_linearize(self, src, R, T, *, src_sid=None, dst_sid=None, stride=1, w_min=0, band=0, r_max=0, g_max=0, huber=0, counts_only=False):
+        """The normal equations of registering a submap of the map `src` against this map at the pose (R, T) that takes source-submap coordinates to
+        this map's: Gauss-Newton on s(R q + T) - t over the observed voxels q of the source whose indices are divisible by `stride` (1, 2, 4, 8, 16),
+        whose weight is at least w_min and whose stored value t lies within `band` of the surface; s is the trilinear interpolant of this map.  Returns
+        the dict of align_linearize: H, b, e (2^-20 fixed point), their float64 forms, the 33 integers (sums) and the counts n_used, n_gate (weight or
+        band), n_unknown (the voxel lands on unobserved voxels of this map), n_far (|s| > r_max), n_grad.  src_sid / dst_sid: submap ids, None = the
+        active submap (submap 0 on a global map).  0 = the default: band = 2 voxels, r_max = internal_voxels * voxel, g_max = 4; huber = 0 is off.
+        `src` may be this map.  Queued frames of both maps are integrated first; neither map is written.  counts_only=True leaves H, b and e at 0 (the
+        A/B switch of tools/bench_register.py)."""
+        cfg = register_config(stride, w_min, band, r_max, g_max, huber, counts_only)
+        sums = _lib.AlignSums()
+        _lib.check(self.L.tsl_tsdf_register_linearize(self.h, -1 if dst_sid is None else int(dst_sid), src.h, -1 if src_sid is None else int(src_sid),
+                                                      _dptr(R, 9)[1], _dptr(T, 3)[1], C.byref(cfg), C.byref(sums)))
+        return align_sums_dict(np.frombuffer(sums, dtype=np.int64))
+
+    def register_submap(self, src, R0, T0, *, levels=None, min_step=1e-4, damping=0.0, min_used=None, src_sid=None, dst_sid=None,
+                        w_min=0, band=0, r_max=0, g_max=0, huber=0):
+        """Refine the pose (R0, T0) that takes a submap of `src` into this map: up to 4 levels (stride, iterations) -- default (4, 4), (2, 4), (1, 6) -- of
+        Gauss-Newton steps on the normal equations of register_linearize, solved and retracted as track_depth does.  Returns (R 3 x 3, T 3, info) shaped
+        like track_depth's: info["status"] 0 the last level ended by min_step, 1 its iterations were exhausted, 2 lost (fewer than min_used voxels
+        used; default 6), 3 singular -- for 2 and 3 the pose returned is the last one that gave a step, or the guess; info["records"] holds for each
+        linearisation its pose, its step xi = (v, omega) and the dict of register_linearize.  The last record's H_f is the information matrix of the
+        constraint.  w_min / band / r_max / g_max / huber: the gates of register_linearize."""
+        cfg = register_config(1, w_min, band, r_max, g_max, huber)
+        tc = _track_config(REGISTER_LEVELS if levels is None else levels, min_step, damping, min_used)
+        Ro, To = np.empty(9, np.float64), np.empty(3, np.float64)
+        rep = _lib.TrackReport()
+        _lib.check(self.L.tsl_tsdf_register_submap(self.h, -1 if dst_sid is None else int(dst_sid), src.h, -1 if src_sid is None else int(src_sid),
+                                                   _dptr(R0, 9)[1], _dptr(T0, 3)[1], C.byref(cfg), C.byref(tc), Ro.ctypes.data_as(_lib.dp),
+                                                   To.ctypes.data_as(_lib.dp), C.byref(rep)))
+        return Ro.reshape(3, 3), To, _track_info(rep)
 
     # ---- ESDF (definition from the legacy dense_esdf.py:228-333; see DESIGN.md) -----------------------------------
     def update_esdf(self, gamma=None, max_dist=None, wait=True):

@@ -13,6 +13,8 @@ no autosave), the send handles default to no-ops, and `recast_depth_to_map(R, T,
 need_create_new_submap with the wrong arity, :205-210) treats every frame as a keyframe."""
 import time
 
+import numpy as np
+
 from . import wire
 from .dense_tsdf import DenseTSDF
 from .taichi_octomap import Octomap
@@ -117,6 +119,25 @@ class SubmapMapping:
 
     def convert_by_pgo(self, frame_id, R, T):
         return self._anchor(frame_id, R, T)
+
+    def register_submaps(self, frame_a, frame_b, **kw):
+        """Register the collection's submap that starts on frame_a (source) against the one that starts on frame_b (destination): whether the two
+        agree where they overlap, as a constraint for the pose graph.  The guess is P_b^-1 P_a from the global map's pose table; returns (R, T, info),
+        the refined pose taking submap a's coordinates to submap b's and DenseTSDF.register_submap's info with "information" (the 6 x 6 matrix H of
+        the last linearisation, float64, twist order (v, omega) in submap b's frame), "guess" (R, T) and "submaps" (sid_a, sid_b).  Nothing moves: no
+        base pose, no map and not the active submap.  kw: the keywords of DenseTSDF.register_submap.  (Not in the reference, which has no registration;
+        TSDF collections only.)"""
+        if self._kind != "tsdf":
+            raise TypeError("register_submaps needs a DenseTSDF collection")
+        sa, sb = self.submaps[frame_a], self.submaps[frame_b]
+        g = self.global_map
+        Ra, Ta, Rb, Tb = g.submaps_base_R_np[sa], g.submaps_base_T_np[sa], g.submaps_base_R_np[sb], g.submaps_base_T_np[sb]
+        R0, T0 = Rb.T @ Ra, Rb.T @ (Ta - Tb)
+        col = self.submap_collection
+        R, T, info = col.register_submap(col, R0, T0, src_sid=sa, dst_sid=sb, **kw)
+        info["information"] = info["records"][-1]["H_f"].copy() if info["records"] else np.zeros((6, 6))
+        info["guess"], info["submaps"] = (R0, T0), (sa, sb)
+        return R, T, info
 
     # ---- submap life cycle -----------------------------------------------------------------------------------------------------------------
     def need_create_new_submap(self, is_keyframe, R=None, T=None):
