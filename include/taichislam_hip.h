@@ -64,7 +64,8 @@ typedef struct {
 
 /* kernel ids for tsl_tsdf_prof_query */
 enum { TSL_K_VOXELIZE = 0, TSL_K_SORT = 1, TSL_K_RAYS = 2, TSL_K_INTEGRATE = 3, TSL_K_FINALIZE = 4,
-       TSL_K_MESH = 5, TSL_K_SEGMENTS = 6, TSL_K_BIN = 7, TSL_K_ESDF = 8, TSL_K_FUSE = 9, TSL_K_REGISTER = 10, TSL_K_COUNT };
+       TSL_K_MESH = 5, TSL_K_SEGMENTS = 6, TSL_K_BIN = 7, TSL_K_ESDF = 8, TSL_K_FUSE = 9, TSL_K_REGISTER = 10,
+       TSL_K_REGISTER_SCORE = 11, TSL_K_COUNT };
 
 const char* tsl_version(void);
 const char* tsl_last_error(void);
@@ -392,6 +393,54 @@ int  tsl_tsdf_register_linearize(tsl_tsdf* dst, int dst_sid, tsl_tsdf* src, int 
                                  const tsl_register_cfg* c, tsl_align_sums* out);
 int  tsl_tsdf_register_submap(tsl_tsdf* dst, int dst_sid, tsl_tsdf* src, int src_sid, const double R0[9], const double T0[3],
                               const tsl_register_cfg* c, const tsl_track_cfg* t, double R_out[9], double T_out[3], tsl_track_report* rep);
+
+/* ---- pose search for the registration (tsl_register_search.hip): many poses scored in one call; a lattice of candidates around a guess, the best
+ * one refined by tsl_tsdf_register_submap.  tsl_tsdf_register_submap is local: from a guess in the basin of another minimum (a room's quarter-turn
+ * alias at a loop closure) it returns a confident wrong pose.  The search scores a window of poses by brute force first.
+ * tsl_tsdf_register_score: out[k] holds e, n_used, n_unknown, n_far and n_grad of the tsl_align_sums that
+ * tsl_tsdf_register_linearize returns for the pose (R + 9 k, T + 3 k) with the same handles, submap ids and tsl_register_cfg: the same stride, gates,
+ * buckets and their order, robust weight, f32 rounding of the pose and order of evaluation.  flags bit 0 (counts only) leaves e at 0.  gate (may be
+ * null) does not depend on the pose: n_gate as in the linearisation, n_pass = the visited voxels that pass the gate, sum_i / sum_j / sum_k the integer
+ * sums of their voxel indices, so (sum / n_pass) * voxel is the centroid of what is being registered.  1 <= n <= 65536.
+ * It is a host form with the contract of tsl_tsdf_register_linearize: it issues the queued frames of both handles, waits for the source's work, runs on
+ * dst's stream, waits, and writes neither map.  dst's export staging buffer holds the counters, the poses, the scores and the list of gated source
+ * voxels (8 bytes each): device pointers from tsl_esdf_export_dev are invalid afterwards.  With profiling on, tsl_tsdf_prof_query(dst,
+ * TSL_K_REGISTER_SCORE) returns the time of the scoring kernel alone (not of the two passes that build the list).
+ * tsl_tsdf_register_score_tile: the entries of the list that one workgroup of the scoring kernel stages for a list of `entries` (= gate.n_pass) and n
+ * poses on dst's device -- 256, halved down to 64 while tiles * ceil(n / 64) < 8 * compute units; 0 for a null handle, entries < 1 or n outside
+ * 1 .. 65536.  It changes no result; tests and tools ask it which tile a case takes.
+ * tsl_tsdf_register_search.  Everything below is host float64 in the written order (tests/register_search_ref.py restates it bit for bit).
+ *   Candidates: n_candidates = the product of the six 2 n + 1 (n_r[0..2], n_t[0..2] are half-counts); the index k runs over (r0, r1, r2, t0, t1, t2),
+ *     the last fastest; an axis' offset is (index - n) * step; omega = the three rotation offsets, v = the three translation offsets.  Tp = T0 - pivot;
+ *     (R, Tp) <- tsl_pose_retract((0, 0, 0, omega), R0, Tp); T = (Tp + pivot) + v: the guess turned about the pivot by the Cayley map of omega -- an
+ *     angle of 2 atan(|omega| / 2), not |omega| -- then shifted.  The candidate with all six offsets zero is (R0, T0) itself, bit for bit.
+ *   Pivot: flags bit 0 = `pivot` is given (dst coordinates).  Otherwise the counting pass of a score at `stride` gives the gate; qbar[a] =
+ *     ((double)sum_a / (double)n_pass) * voxel_scale, pivot[a] = ((R0[a][0] qbar0 + R0[a][1] qbar1) + R0[a][2] qbar2) + T0[a]; n_pass == 0 gives status 2.
+ *   Score: one tsl_tsdf_register_score over all candidates with c's gates and flags at `stride`.  J_k = e + F * n_far + U * (n_unknown + n_grad), all
+ *     int64, F = rint((r_max * r_max) * 2^20), U = rint((miss * miss) * 2^20), the squares in f32 and r_max after its default; miss 0 = r_max: a voxel
+ *     that lands on unknown space costs as much as the worst admissible residual, so poses that slide the source out of the destination never win.
+ *     The overflow refusal of the registration holds with M = max(2 L g_max, g_max, r_max + band, miss): no J can overflow.
+ *   Rank: a candidate is valid iff n_used >= min_used (0 = 6); best = the valid candidate of the least J, ties to the least k (integer comparison).
+ *     No valid candidate: status 2, R_out / T_out = the guess, trk->iterations = 0, best = -1.
+ *   Refine: tsl_tsdf_register_submap from (R_best, T_best) with t and c; rep->status is that run's status 0..3, R_out / T_out and trk (may be null)
+ *     are that run's.  scores (may be null): the n_candidates scores.  rep->gate, rep->pivot, n_valid, J_best and score_best describe the search.
+ * TSL_ERR_ARG (the text names the entry point): everything tsl_tsdf_register_linearize / tsl_tsdf_register_submap refuse, for every pose -- a
+ * non-finite pose anywhere refuses the whole call before anything runs or is written (a search refuses a candidate that is not finite -- a finite
+ * guess far enough out -- before any output is written; the counting pass for an automatic pivot has run by then); n outside 1 .. 65536; a null R / T / out (score), a null
+ * guess / cfg / R_out / T_out / rep (search); a negative half-count, more than 65536 candidates, a non-finite step or pivot, a step <= 0 on an axis
+ * with n > 0, a negative or non-finite miss, a negative min_used, a scoring stride that is not 1, 2, 4, 8 or 16. */
+typedef struct { int64_t e; int32_t n_used, n_unknown, n_far, n_grad; } tsl_register_score;
+typedef struct { int64_t n_gate, n_pass, sum_i, sum_j, sum_k; } tsl_register_gate;
+typedef struct { int32_t n_t[3]; double step_t[3]; int32_t n_r[3]; double step_r[3]; double pivot[3]; int32_t flags; int32_t stride; float miss;
+                 int32_t min_used; } tsl_search_cfg;
+typedef struct { int32_t status, n_candidates, n_valid, best; int64_t J_best; tsl_register_score score_best; double pivot[3], R_best[9], T_best[3];
+                 tsl_register_gate gate; } tsl_search_report;
+int  tsl_tsdf_register_score(tsl_tsdf* dst, int dst_sid, tsl_tsdf* src, int src_sid, const double* R, const double* T, int32_t n,
+                             const tsl_register_cfg* c, tsl_register_score* out, tsl_register_gate* gate);
+int  tsl_tsdf_register_score_tile(tsl_tsdf* dst, int64_t entries, int32_t n);
+int  tsl_tsdf_register_search(tsl_tsdf* dst, int dst_sid, tsl_tsdf* src, int src_sid, const double R0[9], const double T0[3],
+                              const tsl_register_cfg* c, const tsl_search_cfg* s, const tsl_track_cfg* t, double R_out[9], double T_out[3],
+                              tsl_search_report* rep, tsl_track_report* trk, tsl_register_score* scores);
 
 /* backend knobs for A/B-ing kernel variants: name in
      "variant"  0|1: one global int64 atomic pair per ray step, 2 (default): brick-binned LDS accumulation

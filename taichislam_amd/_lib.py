@@ -6,9 +6,10 @@ import os
 from . import build as _build
 
 TSL_OK = 0
-K_VOXELIZE, K_SORT, K_RAYS, K_INTEGRATE, K_FINALIZE, K_MESH, K_SEGMENTS, K_BIN, K_ESDF, K_FUSE, K_REGISTER = range(11)
+K_VOXELIZE, K_SORT, K_RAYS, K_INTEGRATE, K_FINALIZE, K_MESH, K_SEGMENTS, K_BIN, K_ESDF, K_FUSE, K_REGISTER, K_REGISTER_SCORE = range(12)
 KERNEL_NAMES = {K_VOXELIZE: "voxelize", K_SORT: "sort", K_RAYS: "build_rays", K_INTEGRATE: "integrate",
-                K_FINALIZE: "finalize", K_MESH: "marching_cubes", K_SEGMENTS: "segments", K_BIN: "bin", K_ESDF: "esdf", K_FUSE: "fuse", K_REGISTER: "register"}
+                K_FINALIZE: "finalize", K_MESH: "marching_cubes", K_SEGMENTS: "segments", K_BIN: "bin", K_ESDF: "esdf", K_FUSE: "fuse", K_REGISTER: "register",
+                K_REGISTER_SCORE: "register_score"}
 
 
 class TsdfCfg(C.Structure):
@@ -86,6 +87,30 @@ class TrackIter(C.Structure):
 
 class TrackReport(C.Structure):
     _fields_ = [("status", C.c_int32), ("iterations", C.c_int32), ("it", TrackIter * 64)]
+
+
+class RegisterScore(C.Structure):
+    """tsl_register_score (tsl_tsdf_register_score): e and four of the five counts of a linearisation, 24 bytes"""
+    _fields_ = [("e", C.c_int64), ("n_used", C.c_int32), ("n_unknown", C.c_int32), ("n_far", C.c_int32), ("n_grad", C.c_int32)]
+
+
+class RegisterGate(C.Structure):
+    """tsl_register_gate: the pose-independent part of a score call"""
+    _fields_ = [(n, C.c_int64) for n in ("n_gate", "n_pass", "sum_i", "sum_j", "sum_k")]
+
+    def as_dict(self):
+        return {n: int(getattr(self, n)) for n, _ in self._fields_}
+
+
+class SearchCfg(C.Structure):
+    """tsl_search_cfg (tsl_tsdf_register_search): half-counts and steps of the lattice, the pivot (flags bit 0: given), the scoring stride, miss, min_used"""
+    _fields_ = [("n_t", C.c_int32 * 3), ("step_t", C.c_double * 3), ("n_r", C.c_int32 * 3), ("step_r", C.c_double * 3), ("pivot", C.c_double * 3),
+                ("flags", C.c_int32), ("stride", C.c_int32), ("miss", C.c_float), ("min_used", C.c_int32)]
+
+
+class SearchReport(C.Structure):
+    _fields_ = [("status", C.c_int32), ("n_candidates", C.c_int32), ("n_valid", C.c_int32), ("best", C.c_int32), ("J_best", C.c_int64),
+                ("score_best", RegisterScore), ("pivot", C.c_double * 3), ("R_best", C.c_double * 9), ("T_best", C.c_double * 3), ("gate", RegisterGate)]
 
 
 class TslError(RuntimeError):
@@ -179,6 +204,10 @@ SIGNATURES = {
     "tsl_tsdf_track_depth_dev": (C.c_int, [vp, dp, dp, C.POINTER(AlignCfg), C.POINTER(TrackCfg), vp, dp, dp, C.POINTER(TrackReport), vp]),
     "tsl_tsdf_register_linearize": (C.c_int, [vp, C.c_int, vp, C.c_int, dp, dp, C.POINTER(RegisterCfg), C.POINTER(AlignSums)]),
     "tsl_tsdf_register_submap": (C.c_int, [vp, C.c_int, vp, C.c_int, dp, dp, C.POINTER(RegisterCfg), C.POINTER(TrackCfg), dp, dp, C.POINTER(TrackReport)]),
+    "tsl_tsdf_register_score": (C.c_int, [vp, C.c_int, vp, C.c_int, dp, dp, i32, C.POINTER(RegisterCfg), C.POINTER(RegisterScore), C.POINTER(RegisterGate)]),
+    "tsl_tsdf_register_score_tile": (C.c_int, [vp, i64, i32]),
+    "tsl_tsdf_register_search": (C.c_int, [vp, C.c_int, vp, C.c_int, dp, dp, C.POINTER(RegisterCfg), C.POINTER(SearchCfg), C.POINTER(TrackCfg), dp, dp,
+                                           C.POINTER(SearchReport), C.POINTER(TrackReport), C.POINTER(RegisterScore)]),
     "tsl_tsdf_set_option": (C.c_int, [vp, C.c_char_p, C.c_int]),
     "tsl_tsdf_get_option": (C.c_int, [vp, C.c_char_p, C.POINTER(C.c_int)]),
     "tsl_tsdf_prof_enable": (C.c_int, [vp, C.c_int]),

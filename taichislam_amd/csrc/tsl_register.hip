@@ -26,18 +26,11 @@
 #include <cmath>
 #include "tsl_interp.hpp"
 #include "tsl_align_common.hpp"
+#include "tsl_register_common.hpp"
 
 namespace tsl {
 
 #define RG_QUEUE TSL_BRK3              // entries of the LDS queue: every voxel of a brick can pass the gate
-
-struct RegisterDev {
-    float R[9], T[3];                  // source-submap to destination coordinates, rounded to f32 once
-    float vs;
-    float w_min, band, r_max, gm2, huber;      // after the defaults; gm2 = g_max * g_max
-    int smask;                         // stride - 1: an index is on the lattice when (index & smask) == 0 (two's complement: negative indices too)
-    int flags;                         // bit 0: counts only
-};
 
 // At least 3 waves per SIMD: left alone the scheduler overlaps the 28 conversions and takes 194 VGPRs (2 waves); held to 168 it needs no scratch.
 __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) k_register_linearize(MapDev S, int ss, MapDev D, int ds, RegisterDev A, long long* __restrict__ acc)
@@ -164,47 +157,6 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) k
         else { const int c = t - AL_NPROD; sum = ((long long)sc[0][c] + sc[1][c]) + ((long long)sc[2][c] + sc[3][c]); }
         if (sum != 0) __hip_atomic_fetch_add(acc + t, sum, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
-}
-
-static bool rg_finite(float x) { return std::isfinite(x); }
-
-static int rg_slot(const tsl_tsdf* m, int sid) { return m->cfg.is_global_map ? 0 : (sid < 0 ? m->active : sid); }
-
-// the checks and defaults both entry points share; `stride` replaces the configuration's (the levels of the registration)
-static int register_check(tsl_tsdf* dst, int dst_sid, tsl_tsdf* src, int src_sid, const double R[9], const double T[3], const tsl_register_cfg* c, const void* out,
-                          int stride, RegisterDev* A, const char* who)
-{
-    const std::string w(who);
-    TSL_REQUIRE(dst && src, w + ": null handle");
-    TSL_REQUIRE(R && T && c && out, w + ": null argument");
-    TSL_REQUIRE(al_finite(R, 9) && al_finite(T, 3), w + ": the pose is not finite");
-    TSL_REQUIRE(rg_finite(c->w_min) && rg_finite(c->band) && rg_finite(c->r_max) && rg_finite(c->g_max) && rg_finite(c->huber), w + ": w_min / band / r_max / g_max / huber is not finite");
-    TSL_REQUIRE(stride == 1 || stride == 2 || stride == 4 || stride == 8 || stride == 16, w + ": stride must be 1, 2, 4, 8 or 16");
-    TSL_REQUIRE(!(c->w_min < 0.0f) && !(c->band < 0.0f) && !(c->r_max < 0.0f) && !(c->g_max < 0.0f) && !(c->huber < 0.0f), w + ": w_min, band, r_max, g_max and huber must not be negative");
-    TSL_REQUIRE(dst_sid >= -1 && (dst->cfg.is_global_map ? dst_sid <= 0 : dst_sid < dst->nsub), w + ": dst_sid out of range (-1 or 0 on a global map)");
-    TSL_REQUIRE(src_sid >= -1 && (src->cfg.is_global_map ? src_sid <= 0 : src_sid < src->nsub), w + ": src_sid out of range (-1 or 0 on a global map)");
-    TSL_REQUIRE(dst->device == src->device, w + ": the maps live on different devices");
-    TSL_REQUIRE(std::memcmp(&dst->P.vs, &src->P.vs, sizeof(float)) == 0, w + ": the maps have different voxel sizes");
-    for (int i = 0; i < 9; ++i) A->R[i] = (float)R[i];
-    for (int i = 0; i < 3; ++i) A->T[i] = (float)T[i];
-    A->vs = dst->P.vs;
-    A->w_min = c->w_min;
-    A->band = c->band != 0.0f ? c->band : 2.0f * A->vs;
-    A->r_max = c->r_max != 0.0f ? c->r_max : (float)((double)dst->cfg.internal_voxels * dst->cfg.voxel_scale);
-    const float gmax = c->g_max != 0.0f ? c->g_max : 4.0f;
-    A->gm2 = gmax * gmax;
-    A->huber = c->huber;
-    A->smask = stride - 1; A->flags = c->flags;
-    // no sum can overflow: a used voxel has |g_a| <= g_max, |p_a| <= L (its cell is in dst's volume), so |c_a| <= 2 L g_max, and |r| <= |s| + |t| <=
-    // r_max + band; wgt <= 1.  Every product is at most M^2 in magnitude, every addend at most M^2 2^20 + 1/2.  V bounds the visited voxels without a
-    // look at the device: a submap has at most min(max_bricks, nb3) bricks of (16 / stride)^3 lattice voxels.
-    const double L = (double)(dst->M.hN > dst->M.hNz ? dst->M.hN : dst->M.hNz) * dst->cfg.voxel_scale;
-    double Mx = 2.0 * L * (double)gmax;
-    if ((double)gmax > Mx) Mx = (double)gmax;
-    if ((double)A->r_max + (double)A->band > Mx) Mx = (double)A->r_max + (double)A->band;
-    const double per = (double)(16 / stride), V = (double)(src->M.max_bricks < src->M.nb3 ? src->M.max_bricks : src->M.nb3) * per * per * per;
-    TSL_REQUIRE(Mx * Mx * 1048576.0 * V <= 4611686018427387904.0, w + ": the sums could overflow (max(2 L g_max, g_max, r_max + band)^2 * 2^20 * visited voxels exceeds 2^62)");
-    return TSL_OK;
 }
 
 // issues the queued frames of both handles, waits for the source's, and leaves dst's stream with the accumulator in dst's staging buffer

@@ -151,6 +151,29 @@ def _track_info(rep):
     return {"status": int(rep.status), "iterations": int(rep.iterations), "records": records}
 
 
+_SCORE_DTYPE = np.dtype([("e", np.int64), ("n_used", np.int32), ("n_unknown", np.int32), ("n_far", np.int32), ("n_grad", np.int32)])      # tsl_register_score
+
+
+def _scores_dict(a):
+    """The dict of DenseTSDF.register_score from an array of tsl_register_score"""
+    out = {n: a[n].astype(np.int64) for n in _SCORE_DTYPE.names}
+    out["e_f"] = out["e"].astype(np.float64) * ALIGN_SCALE
+    return out
+
+
+def _half_counts(window, step):
+    """(half-counts, steps) of three axes of DenseTSDF.register_search's lattice: round(window / step), 0 for a window of 0; a step may be a scalar.
+    A step that is not positive on an axis with a window is passed on with a half-count of 1, for the library to refuse by name."""
+    steps = [float(s) for s in np.broadcast_to(np.asarray(step, np.float64), (3,))]
+    counts = []
+    for w, s in zip(window, steps):
+        w = float(w)
+        if not np.isfinite(w):
+            raise ValueError("register_search: a window is not finite")
+        counts.append(0 if w == 0.0 else int(round(w / s)) if s > 0.0 and np.isfinite(s) else 1)
+    return counts, steps
+
+
 def _depth_image(depth):
     """(pointer, (h, w), keep-alive, is_device) of a uint16 millimetre image: a numpy array or a torch CUDA tensor, the forms recast_depth_to_map accepts"""
     if _is_device_tensor(depth):
@@ -784,6 +807,75 @@ class DenseTSDF(BaseMap):
                                                    _dptr(R0, 9)[1], _dptr(T0, 3)[1], C.byref(cfg), C.byref(tc), Ro.ctypes.data_as(_lib.dp),
                                                    To.ctypes.data_as(_lib.dp), C.byref(rep)))
         return Ro.reshape(3, 3), To, _track_info(rep)
+
+    # ---- pose search for the registration (tsl_register_search.hip) -------------------------------
+    def register_score(self, src, R, T, *, src_sid=None, dst_sid=None, stride=1, w_min=0, band=0, r_max=0, g_max=0, huber=0, counts_only=False):
+        """Score many poses in one call: for every pose (R[k] 3 x 3, T[k] 3) the e, n_used, n_unknown, n_far and n_grad register_linearize returns for it
+        with the same arguments, without forming H and b.  Returns a dict of int64 arrays [n] under those names, e_f (e * 2^-20, float64) and gate:
+        the pose-independent n_gate, n_pass (the visited voxels that pass the weight and band tests) and sum_i / sum_j / sum_k, the integer sums of
+        their voxel indices -- (sum / n_pass) * voxel is the centroid of what is being registered.  At most 65536 poses.  counts_only=True leaves e
+        at 0.  Queued frames of both maps are integrated first; neither map is written."""
+        R = np.ascontiguousarray(np.asarray(R, np.float64).reshape(-1, 9))
+        T = np.ascontiguousarray(np.asarray(T, np.float64).reshape(-1, 3))
+        if R.shape[0] != T.shape[0]:
+            raise ValueError("register_score: R and T hold different numbers of poses")
+        n = R.shape[0]
+        cfg = register_config(stride, w_min, band, r_max, g_max, huber, counts_only)
+        out = np.zeros(max(n, 1), _SCORE_DTYPE)
+        gate = _lib.RegisterGate()
+        _lib.check(self.L.tsl_tsdf_register_score(self.h, -1 if dst_sid is None else int(dst_sid), src.h, -1 if src_sid is None else int(src_sid),
+                                                  R.ctypes.data_as(_lib.dp), T.ctypes.data_as(_lib.dp), n, C.byref(cfg),
+                                                  out.ctypes.data_as(C.POINTER(_lib.RegisterScore)), C.byref(gate)))
+        return dict(_scores_dict(out[:n]), gate=gate.as_dict())
+
+    def register_score_tile(self, entries, n):
+        """The entries of the list of gated source voxels that one workgroup of the scoring kernel stages when register_score scores n poses
+        against a list of `entries` (= gate["n_pass"]) on this map's device: 256, 128 or 64.  It changes no result; tests and tools ask it which
+        tile a case takes."""
+        return int(self.L.tsl_tsdf_register_score_tile(self.h, int(entries), int(n)))
+
+    def register_search(self, src, R0, T0, *, window_t=(0.8, 0.8, 0.4), step_t=0.2, window_r=(0.0, 0.0, np.pi / 3), step_r=np.pi / 18, pivot=None, stride=4,
+                        miss=0, min_used=None, levels=None, min_step=1e-4, damping=0.0, refine_min_used=None, src_sid=None, dst_sid=None,
+                        w_min=0, band=0, r_max=0, g_max=0, huber=0, return_scores=False):
+        """register_submap with a search in front of it, for a guess that may lie outside the basin of the true pose (a loop closure from a drifted
+        pose table).  A lattice of candidate poses around (R0, T0) -- per axis round(window / step) steps either way; translations in metres along
+        this map's axes, rotations in radians as the vector omega of the Cayley map (an angle of 2 atan(|omega| / 2)) about `pivot`, default: the
+        centroid of the source voxels in the band, carried by the guess -- is scored in one call at `stride`; the cost of a candidate is the integer
+        J = e + F n_far + U (n_unknown + n_grad), F = r_max^2, U = miss^2 in 2^-20 fixed point (miss 0 = r_max): a source voxel that lands on unknown
+        space costs as much as the worst residual admitted.  The candidate of the least J among those with n_used >= min_used (default 6; ties to the
+        first) is refined by register_submap with levels / min_step / damping / refine_min_used.  The default lattice is 9 x 9 x 5 translations
+        x 13 yaw angles = 5265 candidates (at most 65536).  Returns (R, T, info): register_submap's info plus info["search"] = the report (status,
+        n_candidates, n_valid, best, J_best, score_best, pivot, R_best, T_best, gate; scores with return_scores=True).  Status 2 with no records: no
+        candidate was valid, or nothing passed the gate; the pose returned is the guess."""
+        (nt, st), (nr, sr) = _half_counts(window_t, step_t), _half_counts(window_r, step_r)
+        sc = _lib.SearchCfg()
+        for a in range(3):
+            sc.n_t[a], sc.n_r[a], sc.step_t[a], sc.step_r[a] = nt[a], nr[a], st[a], sr[a]
+        if pivot is not None:
+            sc.flags = 1
+            sc.pivot[:] = [float(v) for v in np.asarray(pivot, np.float64).reshape(3)]
+        sc.stride, sc.miss, sc.min_used = int(stride), float(miss), (0 if min_used is None else int(min_used))
+        cfg = register_config(1, w_min, band, r_max, g_max, huber)
+        tc = _track_config(REGISTER_LEVELS if levels is None else levels, min_step, damping, refine_min_used)
+        total = 1
+        for v in nr + nt:
+            total *= 2 * max(v, 0) + 1
+        scores = np.zeros(total, _SCORE_DTYPE) if return_scores and total <= 65536 else None
+        Ro, To = np.empty(9, np.float64), np.empty(3, np.float64)
+        rep, trk = _lib.SearchReport(), _lib.TrackReport()
+        _lib.check(self.L.tsl_tsdf_register_search(self.h, -1 if dst_sid is None else int(dst_sid), src.h, -1 if src_sid is None else int(src_sid),
+                                                   _dptr(R0, 9)[1], _dptr(T0, 3)[1], C.byref(cfg), C.byref(sc), C.byref(tc), Ro.ctypes.data_as(_lib.dp),
+                                                   To.ctypes.data_as(_lib.dp), C.byref(rep), C.byref(trk),
+                                                   None if scores is None else scores.ctypes.data_as(C.POINTER(_lib.RegisterScore))))
+        info = _track_info(trk)
+        sb = rep.score_best
+        info["search"] = {"status": int(rep.status), "n_candidates": int(rep.n_candidates), "n_valid": int(rep.n_valid), "best": int(rep.best),
+                          "J_best": int(rep.J_best), "score_best": {n: int(getattr(sb, n)) for n in ("e", "n_used", "n_unknown", "n_far", "n_grad")},
+                          "pivot": np.array(rep.pivot[:], np.float64), "R_best": np.array(rep.R_best[:], np.float64).reshape(3, 3),
+                          "T_best": np.array(rep.T_best[:], np.float64), "gate": rep.gate.as_dict()}
+        if scores is not None:
+            info["search"]["scores"] = _scores_dict(scores)
+        return Ro.reshape(3, 3), To, info
 
     # ---- ESDF (definition from the legacy dense_esdf.py:228-333; see DESIGN.md) -----------------------------------
     def update_esdf(self, gamma=None, max_dist=None, wait=True):

@@ -127,14 +127,24 @@ class SubmapMapping:
         the last linearisation, float64, twist order (v, omega) in submap b's frame), "guess" (R, T) and "submaps" (sid_a, sid_b).  Nothing moves: no
         base pose, no map and not the active submap.  kw: the keywords of DenseTSDF.register_submap.  (Not in the reference, which has no registration;
         TSDF collections only.)"""
+        return self._constrain("register_submaps", "register_submap", frame_a, frame_b, kw)
+
+    def search_submaps(self, frame_a, frame_b, **kw):
+        """register_submaps with DenseTSDF.register_search in place of register_submap: for a pose table that may have drifted past the basin of
+        the registration (a loop closure).  The same guess P_b^-1 P_a, the same return (R, T, info) with "information", "guess" and "submaps";
+        info["search"] is the search's report.  Nothing moves.  kw: the keywords of DenseTSDF.register_search."""
+        return self._constrain("search_submaps", "register_search", frame_a, frame_b, kw)
+
+    def _constrain(self, who, method, frame_a, frame_b, kw):
+        """register_submaps / search_submaps: the guess from the pose table, the collection's `method` on the two submaps, the fields of the constraint"""
         if self._kind != "tsdf":
-            raise TypeError("register_submaps needs a DenseTSDF collection")
+            raise TypeError(f"{who} needs a DenseTSDF collection")
         sa, sb = self.submaps[frame_a], self.submaps[frame_b]
         g = self.global_map
         Ra, Ta, Rb, Tb = g.submaps_base_R_np[sa], g.submaps_base_T_np[sa], g.submaps_base_R_np[sb], g.submaps_base_T_np[sb]
         R0, T0 = Rb.T @ Ra, Rb.T @ (Ta - Tb)
         col = self.submap_collection
-        R, T, info = col.register_submap(col, R0, T0, src_sid=sa, dst_sid=sb, **kw)
+        R, T, info = getattr(col, method)(col, R0, T0, src_sid=sa, dst_sid=sb, **kw)
         info["information"] = info["records"][-1]["H_f"].copy() if info["records"] else np.zeros((6, 6))
         info["guess"], info["submaps"] = (R0, T0), (sa, sb)
         return R, T, info
