@@ -87,22 +87,30 @@ def _mesh_pair(g, o, thres=0.1, cap=400000):
     return ontri
 
 
-@pytest.mark.parametrize("plane", ["face", "edge", "corner", "inside"])
+@pytest.mark.parametrize("plane", ["face", "edge", "corner", "inside", "slab_face", "slab_edge", "slab_corner"])
 def test_marching_cubes_surface_on_brick_boundaries(hip_lib, plane):
     """The brick sign summary (k_mc_summary) lets the tile kernel skip a brick when it and the seven bricks its cells' corners reach into hold
     values on one side of zero only.  Here the surface lies exactly BETWEEN two storage bricks -- across a face, along an edge, at a corner -- so
     every brick is one-sided by itself and the triangles come from cells whose corners are in the neighbours; then the map changes (the flags
-    of the first mesh are stale) and is meshed again.  marching_cube_mesher.py:127-187."""
+    of the first mesh are stale) and is meshed again.  marching_cube_mesher.py:127-187.
+    slab_*: a volume of 64 x 64 x 48 voxels.  Nz / 2 = 24 = 8 (mod 16), so along z the brick faces lie at k = -24, -8, 8: the zero crossing between the voxels
+    k = 7 | 8 is a brick face there and nowhere in a cube; the face, edge and corner variants all involve z."""
     from taichislam_amd.mapping import DenseTSDF
     from oracle import OracleTSDF
-    cfg = dict(map_scale=[3.2, 3.2], voxel_scale=0.05, num_voxel_per_blk_axis=16)
+    slab = plane.startswith("slab_")
+    plane = plane[5:] if slab else plane
+    cfg = dict(map_scale=[3.2, 2.4] if slab else [3.2, 3.2], voxel_scale=0.05, num_voxel_per_blk_axis=16)
     g, o = DenseTSDF(**cfg), OracleTSDF(**cfg)
+    assert (g.N, g.Nz) == (o.N, o.Nz) == ((64, 48) if slab else (64, 64))
     r = np.arange(-24, 24, dtype=np.int16)                                  # three bricks per axis around the origin (brick faces at multiples of 16 from -32)
     ii, jj, kk = np.meshgrid(r, r, r, indexing="ij")
     idx = np.stack([ii, jj, kk], -1).reshape(-1, 3)
     x, y, z = (idx[:, a].astype(np.float32) for a in range(3))
     c = -0.5 if plane != "inside" else 3.3                                   # the zero crossing between voxels -1 | 0 = between two bricks
     d = {"face": x - c, "edge": np.maximum(x - c, y - c), "corner": np.maximum(np.maximum(x - c, y - c), z - c), "inside": x - c}[plane]
+    if slab:
+        cz = 7.5                                                             # between k = 7 | 8
+        d = {"face": z - cz, "edge": np.maximum(x - c, z - cz), "corner": np.maximum(np.maximum(x - c, y - c), z - cz)}[plane]
     t = (d * np.float32(0.05)).astype(np.float16)
 
     def load(tt):

@@ -25,6 +25,9 @@ BLK10 = ["blk10_two_submaps", "blk10_two_submaps_fused"]
 # a submap with a tilted base pose, a display window, recast_step = 3 on an image of 61 rows, internal_voxels = 3, voxels of 12 cm: map, particle exports
 # (positions through the submap's pose), ray casts, meshes at step 1 and 2
 POSED = ["posed_exports"]
+# a flat slab, the shape of the reference's own node (map_size_xy = 100, map_size_z = 10): N = 128, Nz = 48 (a global map of N = 256, Nz = 48), 8 x 8 x 3 storage bricks
+# whose faces along z lie at k = -8 and 8 (Nz / 2 = 24 = 8 mod 16), inside the data; the inputs stay inside the slab (the reference has no bounds check)
+SLABS = ["slab_exports", "slab_two_submaps_fused"]
 
 
 def load(name):
@@ -99,7 +102,7 @@ class _Ora:
             self.o.integrate_points(s["R"], s["T"], s["xyz"], s.get("rgb"), mode=mode)
 
 
-@pytest.mark.parametrize("name", NAMES + BLK10 + POSED)
+@pytest.mark.parametrize("name", NAMES + BLK10 + POSED + SLABS)
 def test_oracle_faithful_reproduces_the_reference_source_bit_for_bit(name):
     from oracle import FAITHFUL
     cfg, K, Kc, steps, want = load(name)
@@ -116,7 +119,18 @@ def test_the_vectors_cover_what_they_claim():
     assert "color" in t and (t["color"] != 0).any()
     _, _, _, steps, p = load("point_clouds")
     assert p["indices"].shape[0] > 10000 and sum(s["kind"] == "pcl" for s in steps) == 2
-    assert sorted(os.path.basename(f) for f in glob.glob(os.path.join(GOLD, "ref_*.npz"))) == sorted(f"ref_{n}.npz" for n in NAMES + BLK10 + POSED + ["octomap", "session", "session_blk10", "esdf_defs"])
+    assert sorted(os.path.basename(f) for f in glob.glob(os.path.join(GOLD, "ref_*.npz"))) == sorted(f"ref_{n}.npz" for n in NAMES + BLK10 + POSED + SLABS + ["octomap", "octomap_slab", "session", "session_blk10", "esdf_defs"])
+
+
+def test_the_slab_vectors_cover_what_they_claim():
+    """the slabs are slabs, and their data crosses the brick faces that a cube of the same bricks does not have (k = -8 and 8)"""
+    for n in SLABS:
+        cfg, _, _, steps, e = load(n)
+        scale = [s for s in steps if s["kind"] == "fuse"][0]["global_map_scale"] if n.endswith("fused") else cfg["map_scale"]
+        assert scale[0] > 2 * scale[1] and round(scale[1] / cfg["voxel_scale"]) % 32 == 16
+        assert e["indices"][:, 2].min() < -8 and e["indices"][:, 2].max() > 8 and np.abs(e["indices"][:, 2]).max() < round(scale[1] / cfg["voxel_scale"]) // 2
+    cfg, _, _, _, e = load("octomap_slab")
+    assert cfg["map_scale"] == [6.4, 3.2] and e["indices"][:, 2].min() < -16 and e["indices"][:, 2].max() > 16
 
 
 # ------------------------------------------------------------------------------------------------------------------ HIP (GPU)
@@ -142,7 +156,7 @@ class _Hip:
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("name", ["depth_stream", "point_clouds", "weight_clamp", "textured", "textured_points", "blk10_two_submaps"])
+@pytest.mark.parametrize("name", ["depth_stream", "point_clouds", "weight_clamp", "textured", "textured_points", "blk10_two_submaps", "slab_exports"])
 def test_hip_sequential_mode_reproduces_the_reference_source_bit_for_bit(hip_lib, name):
     cfg, K, Kc, steps, want = load(name)
     got = replay(lambda over: _Hip({**cfg, **over}, K, Kc, 1), steps, K, Kc, {}, None)
@@ -150,7 +164,7 @@ def test_hip_sequential_mode_reproduces_the_reference_source_bit_for_bit(hip_lib
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("name", NAMES)
+@pytest.mark.parametrize("name", NAMES + SLABS)
 def test_hip_default_path_against_the_reference_source(hip_lib, name):
     """The order-free default: the same voxels observed, the same occupancy; TSDF within the band BASELINE.md section 5 measures against the literal
     replay (per-frame sums applied once instead of ray by ray in f16: a few f16 ulp per frame)."""
@@ -186,9 +200,9 @@ def _octo_replay(o, steps, depth_fn, pcl_fn):
     return idx[order].astype(np.int16), cnt[order].astype(np.float32)
 
 
-def test_oracle_octomap_reproduces_the_reference_source_bit_for_bit():
+def _oracle_octomap_check(name):
     from oracle import OracleOctomap
-    cfg, K, _, steps, want = load("octomap")
+    cfg, K, _, steps, want = load(name)
     o = OracleOctomap(**cfg)
     o.set_intrinsics(K, K)
     idx, cnt = _octo_replay(o, steps, lambda s: o.integrate_depth(s["R"], s["T"], s["depth"], None), lambda s: o.integrate_points(s["R"], s["T"], s["xyz"], None))
@@ -196,12 +210,18 @@ def test_oracle_octomap_reproduces_the_reference_source_bit_for_bit():
     assert np.array_equal(idx, want["indices"]) and np.array_equal(cnt.view(np.uint32), want["occupy"].view(np.uint32))
 
 
-@pytest.mark.parametrize("textured", [False, True])
-def test_oracle_octomap_exports_reproduce_the_reference_source(textured):
-    """cvt_occupy_to_voxels(level) of the reference (taichi_octomap.py:90-102; the node calls it with level 0) on a submap with a tilted base pose: the leaves above
-    min_occupy_thres, positions through the pose, colours of the textured tree -- the same rows, bit for bit, at level 0 and 1."""
+def test_oracle_octomap_reproduces_the_reference_source_bit_for_bit():
+    _oracle_octomap_check("octomap")
+
+
+def test_oracle_octomap_reproduces_the_reference_source_bit_for_bit_on_a_slab():
+    """map_scale = [6.4, 3.2]: Rxy = 7, Rz = 6, the last level of the tree has cells of K x K x 1 (taichi_octomap.py:66-70)"""
+    _oracle_octomap_check("octomap_slab")
+
+
+def _oracle_octomap_exports_check(name, textured):
     from oracle import OracleOctomap
-    cfg, K, _, steps, want = load("octomap")
+    cfg, K, _, steps, want = load(name)
     o = OracleOctomap(**{**cfg, "texture_enabled": textured})
     o.set_intrinsics(K, K)
     o.set_base_pose_submap(0, want["posed_R"], want["posed_T"])
@@ -218,14 +238,35 @@ def test_oracle_octomap_exports_reproduce_the_reference_source(textured):
         assert n == w.shape[0] > 500 and np.array_equal(got.view(np.uint32), w.view(np.uint32)), level
 
 
-@pytest.mark.gpu
-def test_hip_octomap_reproduces_the_reference_source_bit_for_bit(hip_lib):
+@pytest.mark.parametrize("textured", [False, True])
+def test_oracle_octomap_exports_reproduce_the_reference_source(textured):
+    """cvt_occupy_to_voxels(level) of the reference (taichi_octomap.py:90-102; the node calls it with level 0) on a submap with a tilted base pose: the leaves above
+    min_occupy_thres, positions through the pose, colours of the textured tree -- the same rows, bit for bit, at level 0 and 1."""
+    _oracle_octomap_exports_check("octomap", textured)
+
+
+@pytest.mark.parametrize("textured", [False, True])
+def test_oracle_octomap_exports_reproduce_the_reference_source_on_a_slab(textured):
+    _oracle_octomap_exports_check("octomap_slab", textured)
+
+
+def _hip_octomap_check(name):
     from taichislam_amd.mapping import Octomap
-    cfg, K, _, steps, want = load("octomap")
+    cfg, K, _, steps, want = load(name)
     o = Octomap(**cfg)
     o.set_dep_camera_intrinsic(K)
     idx, cnt = _octo_replay(o, steps, lambda s: o.recast_depth_to_map(s["R"], s["T"], s["depth"], None), lambda s: o.recast_pcl_to_map(s["R"], s["T"], s["xyz"], None, s["xyz"].shape[0]))
     assert np.array_equal(idx, want["indices"]) and np.array_equal(cnt.view(np.uint32), want["occupy"].view(np.uint32))
+
+
+@pytest.mark.gpu
+def test_hip_octomap_reproduces_the_reference_source_bit_for_bit(hip_lib):
+    _hip_octomap_check("octomap")
+
+
+@pytest.mark.gpu
+def test_hip_octomap_reproduces_the_reference_source_bit_for_bit_on_a_slab(hip_lib):
+    _hip_octomap_check("octomap_slab")
 
 
 # ------------------------------------------------------------------------------------------------------------------ marching cubes (marching_cube_mesher.py)
@@ -268,7 +309,7 @@ def _hip_map(name, **extra):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("name", ["depth_stream", "textured"])
+@pytest.mark.parametrize("name", ["depth_stream", "textured", "slab_exports"])
 def test_hip_mesh_reproduces_the_reference_source_bit_for_bit(hip_lib, name):
     from taichislam_amd.mapping import MarchingCubeMesher
     cfg, m, want = _hip_map(name)
@@ -281,7 +322,7 @@ def test_hip_mesh_reproduces_the_reference_source_bit_for_bit(hip_lib, name):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("name", ["depth_stream", "textured"])
+@pytest.mark.parametrize("name", ["depth_stream", "textured", "slab_exports"])
 def test_hip_coarse_mesh_and_the_gather_kernel_reproduce_the_reference_source(hip_lib, name):
     """generate_mesh(2) -- cubes of edge 2 anchored at every voxel, corners up to two voxels beyond the brick: every value is read through the brick
     table (k_marching_cubes) -- and the same kernel at step 1 (option mesh_gather) against the reference's own meshes."""
@@ -316,7 +357,7 @@ def _oracle_map(name):
     return cfg, o, want
 
 
-@pytest.mark.parametrize("name", ["depth_stream", "textured"] + POSED)
+@pytest.mark.parametrize("name", ["depth_stream", "textured"] + POSED + ["slab_exports"])
 def test_oracle_exports_raycast_and_mesh_reproduce_the_reference_source(name):
     """On the reference's map: cvt_TSDF_surface_to_voxels (positions + colours: the jet colour map of matplotlib, or the stored colours), cvt_TSDF_to_voxels_slice,
     BaseMap.raycast for 24 rays, and generate_mesh(1) with vertex colours -- everything bit for bit, as sets of rows."""
@@ -342,7 +383,7 @@ def test_oracle_exports_raycast_and_mesh_reproduce_the_reference_source(name):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("name", ["depth_stream", "textured"])
+@pytest.mark.parametrize("name", ["depth_stream", "textured", "slab_exports"])
 def test_hip_exports_and_raycast_reproduce_the_reference_source(hip_lib, name):
     """The HIP map of semantics = 1 is the reference's map bit for bit (colours included); so are its particle exports and ray casts."""
     cfg, m, want = _hip_map(name, max_disp_particles=40000)
@@ -488,28 +529,45 @@ def _octo_textured(o, z, depth_fn, export):
     assert np.array_equal(rgb[order].astype(np.float32).view(np.uint32), z["out_tex_color"].view(np.uint32)), "leaf colours (last writer, BGR -> RGB, / 255)"
 
 
-def test_oracle_textured_octomap_reproduces_the_reference_source():
+def _oracle_textured_octomap_check(name):
     from oracle import OracleOctomap
-    cfg, K, _, _, _ = load("octomap")
-    z = np.load(os.path.join(GOLD, "ref_octomap.npz"))
+    cfg, K, _, _, _ = load(name)
+    z = np.load(os.path.join(GOLD, f"ref_{name}.npz"))
     o = OracleOctomap(**{**cfg, "texture_enabled": True})
     o.set_intrinsics(K, K)
     _octo_textured(o, z, lambda R, T, d, t: o.integrate_depth(R, T, d, t), lambda: o.export_leaves(with_color=True))
 
 
-@pytest.mark.gpu
-def test_hip_textured_octomap_reproduces_the_reference_source(hip_lib):
+def test_oracle_textured_octomap_reproduces_the_reference_source():
+    _oracle_textured_octomap_check("octomap")
+
+
+def test_oracle_textured_octomap_reproduces_the_reference_source_on_a_slab():
+    _oracle_textured_octomap_check("octomap_slab")
+
+
+def _hip_textured_octomap_check(name):
     from taichislam_amd.mapping import Octomap
-    cfg, K, _, _, _ = load("octomap")
-    z = np.load(os.path.join(GOLD, "ref_octomap.npz"))
+    cfg, K, _, _, _ = load(name)
+    z = np.load(os.path.join(GOLD, f"ref_{name}.npz"))
     o = Octomap(**{**cfg, "texture_enabled": True})
     o.set_dep_camera_intrinsic(K); o.set_color_camera_intrinsic(K)
     _octo_textured(o, z, lambda R, T, d, t: o.recast_depth_to_map(R, T, d, t), lambda: o.export_leaves(with_color=True))
 
 
+@pytest.mark.gpu
+def test_hip_textured_octomap_reproduces_the_reference_source(hip_lib):
+    _hip_textured_octomap_check("octomap")
+
+
+@pytest.mark.gpu
+def test_hip_textured_octomap_reproduces_the_reference_source_on_a_slab(hip_lib):
+    _hip_textured_octomap_check("octomap_slab")
+
+
 # ------------------------------------------------------------------------------------------------------------------ the literal fusion on the GPU
 @pytest.mark.gpu
-@pytest.mark.parametrize("name", list(FUSED) + ["blk10_two_submaps_fused"])
+@pytest.mark.parametrize("name", list(FUSED) + ["blk10_two_submaps_fused", "slab_two_submaps_fused"])
 def test_hip_sequential_fusion_reproduces_the_reference_source_bit_for_bit(hip_lib, name):
     """semantics = 1 on the submaps AND on the global map: integration and fusion both replay the reference literally (csrc/tsl_sequential.hip) -- the fused
     global maps of the reference's own source, NaNs of the axis-aligned case included, bit for bit.  blk10: blocks of 10 voxels, the reference's own

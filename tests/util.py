@@ -7,6 +7,12 @@ C2 = dict(map_scale=[10.24, 10.24], voxel_scale=0.02, num_voxel_per_blk_axis=16,
           min_ray_length=0.3, internal_voxels=10, recast_step=2, texture_enabled=False)
 SMALL = dict(map_scale=[10.24, 10.24], voxel_scale=0.04, num_voxel_per_blk_axis=16, max_ray_length=5.0,
              min_ray_length=0.3, internal_voxels=10, recast_step=2, texture_enabled=False)
+# volumes whose height differs from their width (the reference's node maps a flat slab: map_size_xy = 100, map_size_z = 10).  SLAB: N = 144, Nz = 48,
+# 9 x 9 x 3 bricks, and N / 2 = 72, Nz / 2 = 24 are both 8 (mod 16): the brick faces lie at voxel indices 8 (mod 16) on every axis.  TALL: N = 64,
+# Nz = 128, more bricks along z than along x (with tall_stream).  GSLAB: the global map two SLAB submaps are fused into, N = 256, Nz = 64.
+SLAB = dict(SMALL, map_scale=[5.76, 1.92])
+TALL = dict(SMALL, map_scale=[2.56, 5.12])
+GSLAB = dict(SLAB, map_scale=[10.24, 2.4], is_global_map=True)
 
 
 def lin(idx):
@@ -49,6 +55,20 @@ def small_stream(n, h=120, w=160, **kw):
         R, T = syn.camera_pose(f, **{k: v for k, v in kw.items() if k in ("orbit", "start_deg")})
         frames.append((R, T, syn.sphere_room_depth(R, T, h, w, radius=kw.get("radius", 3.0), K=K)))
     return K, frames
+
+
+def tall_stream(n):
+    """small_stream(n, radius=2.0) with every pose turned by Q (x -> z, z -> -x): the same depth images, seen by a camera that looks up the z axis of TALL"""
+    Q = np.array([[0.0, 0, -1], [0, 1, 0], [1, 0, 0]])
+    K, frames = small_stream(n, radius=2.0)
+    return K, [(Q @ R, Q @ T, d) for R, T, d in frames]
+
+
+def tilt(R, a, b):
+    """R turned by a about z, then by b about x: a base pose off the lattice (with an axis-aligned one six of the seven splat weights of a fusion are exactly
+    0); the tilt() of tools/gen_ref_golden.py, which keeps its own so that the generator needs nothing of this file"""
+    ca, sa, cb, sb = np.cos(a), np.sin(a), np.cos(b), np.sin(b)
+    return R @ np.array([[ca, -sa, 0], [sa, ca, 0], [0, 0, 1.0]]) @ np.array([[1.0, 0, 0], [0, cb, -sb], [0, sb, cb]])
 
 
 def make_pair(cfg, K, **gpu_kw):

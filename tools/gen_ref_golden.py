@@ -8,7 +8,7 @@ tests/golden/ref_*.npz.  tests/test_ref_golden.py then checks, where the referen
   * oracle FAITHFUL (the reference-literal sequential replay) == these maps, bit for bit           (CPU, -m "not gpu")
   * HIP semantics = 1 == these maps, bit for bit; the default HIP path: same voxel set, bounded deviation   (GPU)
 
-    python tools/gen_ref_golden.py            # ~3 minutes; needs /root/reference"""
+    python tools/gen_ref_golden.py [NAME ...]   # ~6 minutes for everything; needs /root/reference"""
 import importlib.util
 import json
 import os
@@ -143,6 +143,23 @@ def scenarios():
     out.append(("posed_exports", cfg3, K3, None, fr3))
     out.append(("blk10_two_submaps_fused", cfg10, K, None, tilted))
     out.append(("blk10_two_submaps", cfg10, K, None, [s for s in tilted if s["kind"] != "fuse"] + [dict(kind="select", sid=1)]))
+    # 9. a flat slab, the shape of the reference's own node (taichislam_node.py: map_size_xy = 100, map_size_z = 10): N = 128, Nz = 48, 8 x 8 x 3 bricks, and
+    #    N / 2 = 64 but Nz / 2 = 24 = 8 (mod 16) -- along z the faces of the 16^3 storage bricks lie at k = -8 and 8, inside the data.  The reference has no
+    #    bounds check (outside the volume is undefined), so everything stays inside the slab: a wide, low image keeps the rays near the horizontal, the submaps'
+    #    base poses are level (a camera-optical base pose would stand the slab on its side), the camera poses are those of scenario 5.
+    hs, ws = 20, 64
+    Ks = syn.scaled_intrinsics(hs, ws)
+    cfgs = dict(map_scale=[6.4, 2.4], voxel_scale=0.05, num_voxel_per_blk_axis=16, max_ray_length=4.0, min_ray_length=0.3, internal_voxels=5, recast_step=2, max_submap_num=4)
+    B0, B1 = tilt(eye, 0.17, 0.05), tilt(eye, -0.11, 0.08)
+    T0b = T0 + np.array([0.04, -0.02, 0.03])
+    #    (recast_step = 1: with every second pixel the step-1 mesh of this scene has 14 triangles, with every pixel 2408)
+    out.append(("slab_exports", {**cfgs, "recast_step": 1, "disp_floor": -0.6, "disp_ceiling": 0.9}, Ks, None,
+                [dict(kind="base", sid=0, R=B0, T=T0), dict(kind="depth", R=R0, T=T0, depth=syn.sphere_room_depth(R0, T0, hs, ws, radius=2.5, K=Ks)),
+                 dict(kind="depth", R=R0, T=T0b, depth=syn.sphere_room_depth(R0, T0b, hs, ws, radius=2.5, K=Ks))]))
+    out.append(("slab_two_submaps_fused", cfgs, Ks, None,
+                [dict(kind="base", sid=0, R=B0, T=T0), dict(kind="depth", R=R0, T=T0, depth=syn.sphere_room_depth(R0, T0, hs, ws, radius=2.5, K=Ks)),
+                 dict(kind="next_submap"), dict(kind="base", sid=1, R=B1, T=T1), dict(kind="depth", R=R1, T=T1, depth=syn.sphere_room_depth(R1, T1, hs, ws, radius=2.5, K=Ks)),
+                 dict(kind="next_submap"), dict(kind="fuse", global_map_scale=[12.8, 2.4])]))
     return out
 
 
@@ -151,7 +168,8 @@ def canon_rows(*cols):
     return t[np.lexsort(t.view(np.uint32).T[::-1])]
 
 
-WITH_EXPORTS = ("depth_stream", "textured", "posed_exports")
+WITH_EXPORTS = ("depth_stream", "textured", "posed_exports", "slab_exports")
+FLAT = ("slab_exports",)         # rays and query points that stay inside a slab: the reference's raycast and point queries have no bounds check either
 
 
 def run(DenseTSDF, name, cfg, K, Kc, steps):
@@ -218,6 +236,9 @@ def run(DenseTSDF, name, cfg, K, Kc, steps):
         last = [s for s in steps if s["kind"] == "depth"][-1]
         rng = np.random.default_rng(3)
         d = rng.normal(size=(24, 3)); d /= np.linalg.norm(d, axis=1, keepdims=True)
+        if name in FLAT:                                # within 17 degrees of the horizontal: 3 m of ray rise by less than 0.9 m
+            phi = np.arctan2(d[:, 1], d[:, 0])
+            d = np.stack([np.cos(phi), np.sin(phi), 0.3 * d[:, 2]], axis=1); d /= np.linalg.norm(d, axis=1, keepdims=True)
         pos = np.tile(np.asarray(m.input_T[None].to_list(), dtype=np.float64).astype(np.float32), (24, 1)) + rng.uniform(-0.05, 0.05, size=(24, 3)).astype(np.float32)
         hit, end, ln = [], [], []
         for a, b in zip(pos, d.astype(np.float32)):
@@ -238,27 +259,43 @@ def run(DenseTSDF, name, cfg, K, Kc, steps):
     return res
 
 
-def run_octomap(Octomap):
+def run_octomap(Octomap, name="octomap", cfg_over=None, zclip=None):
     """taichi_octomap.py: two depth frames and a point cloud into the occupancy tree; the leaves (index, count) are read from the stand-in's
     storage (the reference's Octomap exports nothing but display particles).  Its fuse_submaps is not part of the vector: untextured it
-    stops with AttributeError ('Octomap' object has no attribute 'color', taichi_octomap.py:198), textured its result is a last-writer race."""
+    stops with AttributeError ('Octomap' object has no attribute 'color', taichi_octomap.py:198), textured its result is a last-writer race.
+    `cfg_over` changes the configuration (a slab: Rxy != Rz); with `zclip` the pixels and points that leave |z| < zclip in a map's frame are
+    dropped from the inputs -- the reference's tree has no bounds check, below its floor at -map_size_z / 2 is undefined."""
     from taichislam_amd.utils import synthetic as syn
     rng = np.random.default_rng(7)
     h, w = 30, 40
     K = syn.scaled_intrinsics(h, w)
-    cfg = dict(map_scale=[6.4, 6.4], voxel_scale=0.05, min_occupy_thres=1, max_ray_length=3.0, min_ray_length=0.3, K=2, max_submap_num=4, recast_step=1)
+    cfg = {**dict(map_scale=[6.4, 6.4], voxel_scale=0.05, min_occupy_thres=1, max_ray_length=3.0, min_ray_length=0.3, K=2, max_submap_num=4, recast_step=1), **(cfg_over or {})}
+    ca, sa = np.cos(0.23), np.sin(0.23)
+    Rb, Tb = np.array([[ca, -sa, 0], [sa, ca, 0], [0, 0, 1.0]]) @ np.array([[1.0, 0, 0], [0, np.cos(0.1), -np.sin(0.1)], [0, np.sin(0.1), np.cos(0.1)]]), np.array([0.21, -0.13, 0.07])
+
+    def clipped(depth, R, T):           # the depth image without the pixels whose point leaves |z| < zclip in the frame of either base pose used below
+        if zclip is None:
+            return depth
+        jj, ii = np.mgrid[0:h, 0:w]
+        dep = depth.astype(np.float64) / 1000.0
+        Km = np.asarray(K, np.float64).reshape(3, 3)
+        p = np.stack([(ii - Km[0, 2]) * dep / Km[0, 0], (jj - Km[1, 2]) * dep / Km[1, 1], dep], -1) @ np.asarray(R).T + np.asarray(T)
+        keep = (np.abs(p[..., 2]) < zclip) & (np.abs(((p - Tb) @ Rb)[..., 2]) < zclip)
+        return np.where(keep, depth, 0).astype(depth.dtype)
     m = Octomap(**cfg, max_disp_particles=64)
     m.set_dep_camera_intrinsic(K)
     m.set_base_pose_submap(0, np.eye(3), np.zeros(3))
     steps, t0 = [dict(kind="base", sid=0, R=np.eye(3), T=np.zeros(3))], time.time()
     for f in range(2):
         R, T = syn.camera_pose(5 * f, orbit=0.2)
-        depth = syn.sphere_room_depth(R, T, h, w, radius=1.6, K=K)
+        depth = clipped(syn.sphere_room_depth(R, T, h, w, radius=1.6, K=K), R, T)
         m.recast_depth_to_map(R, T, depth, np.zeros((1, 1, 3), np.uint8))
         steps.append(dict(kind="depth", R=R, T=T, depth=depth))
     d = rng.normal(size=(300, 3)); d /= np.linalg.norm(d, axis=1, keepdims=True)
     pts = np.concatenate([d * rng.uniform(0.3, 2.5, size=(300, 1)), np.array([[0.4, -0.3, 0.6]]) + rng.uniform(-0.02, 0.02, size=(50, 3))]).astype(np.float32)
     Rp = np.array([[0.0, -1.0, 0], [1.0, 0, 0], [0, 0, 1.0]]); Tp = np.array([0.05, 0.1, -0.02])
+    if zclip is not None:
+        pts = pts[np.abs((pts.astype(np.float64) @ Rp.T + Tp)[:, 2]) < zclip]
     m.recast_pcl_to_map(Rp, Tp, pts, np.zeros((1, 3), np.uint8), pts.shape[0])
     steps.append(dict(kind="pcl", R=Rp, T=Tp, xyz=pts))
     def leaves(o, colour=False):
@@ -279,7 +316,7 @@ def run_octomap(Octomap):
     mt.set_dep_camera_intrinsic(K); mt.set_color_camera_intrinsic(K)
     mt.set_base_pose_submap(0, np.eye(3), np.zeros(3))
     R, T = syn.camera_pose(2, orbit=0.2)
-    depth = syn.sphere_room_depth(R, T, h, w, radius=1.6, K=K)
+    depth = clipped(syn.sphere_room_depth(R, T, h, w, radius=1.6, K=K), R, T)
     tex = rng.integers(0, 256, size=(h, w, 3), dtype=np.uint8)
     mt.recast_depth_to_map(R, T, depth, tex)
     ct = leaves(mt, True)
@@ -287,8 +324,6 @@ def run_octomap(Octomap):
                 "tex_occupy": np.array([c[3] for c in ct], np.float32), "tex_color": np.array([c[4:] for c in ct], np.float32)})
     # cvt_occupy_to_voxels(level) (taichi_octomap.py:90-102; the node calls it with level 0): the leaves above min_occupy_thres, positions through the
     # submap's base pose (a tilted one here) -- as rows in a canonical order, untextured and textured
-    ca, sa = np.cos(0.23), np.sin(0.23)
-    Rb, Tb = np.array([[ca, -sa, 0], [sa, ca, 0], [0, 0, 1.0]]) @ np.array([[1.0, 0, 0], [0, np.cos(0.1), -np.sin(0.1)], [0, np.sin(0.1), np.cos(0.1)]]), np.array([0.21, -0.13, 0.07])
     for tag, textured in (("posed", False), ("posedtex", True)):
         mp = Octomap(**{**cfg, "texture_enabled": textured}, max_disp_particles=40000)
         mp.set_dep_camera_intrinsic(K); mp.set_color_camera_intrinsic(K)
@@ -303,10 +338,11 @@ def run_octomap(Octomap):
             res[f"{tag}_export{level}"] = canon_rows(*cols)
         print(f"  {tag}: {n_} particles above the threshold")
     res["posed_R"], res["posed_T"] = Rb, Tb
-    print(f"octomap: {len(cells)} leaves, {time.time() - t0:.1f} s")
+    print(f"{name}: {len(cells)} leaves, k {min(c[2] for c in cells)} .. {max(c[2] for c in cells)}, {time.time() - t0:.1f} s")
     return cfg, K, steps, res
 
 
+OCTOMAP_SLAB = dict(name="octomap_slab", cfg_over=dict(map_scale=[6.4, 3.2]), zclip=1.5)
 SESSION = dict(H=48, W=64, OPTS=dict(map_scale=[10.24, 10.24], voxel_scale=0.08, num_voxel_per_blk_axis=16, max_ray_length=5.0, max_submap_num=16, max_disp_particles=64))
 
 
@@ -368,6 +404,9 @@ if __name__ == "__main__":
     if not only or "octomap" in only:
         cfg, K, steps, res = run_octomap(Octomap)
         save("octomap", cfg, K, None, steps, res)
+    if not only or "octomap_slab" in only:      # a slab: Rxy = 7, Rz = 6 -- the last level of the tree has cells of K x K x 1
+        cfg, K, steps, res = run_octomap(Octomap, **OCTOMAP_SLAB)
+        save("octomap_slab", cfg, K, None, steps, res)
     if not only or "session" in only:
         run_session(DenseTSDF, Octomap)
     if not only or "session_blk10" in only:     # the same session with the block size of the reference's own configuration (submap_mapping.py:33-36)
