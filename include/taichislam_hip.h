@@ -65,7 +65,8 @@ typedef struct {
 /* kernel ids for tsl_tsdf_prof_query */
 enum { TSL_K_VOXELIZE = 0, TSL_K_SORT = 1, TSL_K_RAYS = 2, TSL_K_INTEGRATE = 3, TSL_K_FINALIZE = 4,
        TSL_K_MESH = 5, TSL_K_SEGMENTS = 6, TSL_K_BIN = 7, TSL_K_ESDF = 8, TSL_K_FUSE = 9, TSL_K_REGISTER = 10,
-       TSL_K_REGISTER_SCORE = 11, TSL_K_COUNT };
+       TSL_K_REGISTER_SCORE = 11, TSL_K_FRONTIER_MARK = 12, TSL_K_FRONTIER_LABEL = 13, TSL_K_FRONTIER_JOIN = 14, TSL_K_FRONTIER_SUM = 15,
+       TSL_K_FRONTIER_EMIT = 16, TSL_K_COUNT };
 
 const char* tsl_version(void);
 const char* tsl_last_error(void);
@@ -441,6 +442,42 @@ int  tsl_tsdf_register_score_tile(tsl_tsdf* dst, int64_t entries, int32_t n);
 int  tsl_tsdf_register_search(tsl_tsdf* dst, int dst_sid, tsl_tsdf* src, int src_sid, const double R0[9], const double T0[3],
                               const tsl_register_cfg* c, const tsl_search_cfg* s, const tsl_track_cfg* t, double R_out[9], double T_out[3],
                               tsl_search_report* rep, tsl_track_report* trk, tsl_register_score* scores);
+
+/* ---- exploration frontiers (tsl_frontier.hip): where the known map ends -- the free voxels that border unobserved space, grouped into connected
+ * clusters, the targets of an exploration planner.  The reference tests a frontier per facelet inside its topology graph (topo_graph.py), which is out
+ * of scope; this is the map pass behind it, defined by the project.  Everything is integer except one f32 comparison: the
+ * result depends on no schedule and tests/frontier_ref.py restates it bit for bit.  The pass reads one submap slot, the one of tsl_tsdf_query_points
+ * (the active submap; submap 0 on a global map), and writes nothing to the map.
+ *   Classes.  A voxel (i, j, k) inside the volume is UNKNOWN when its brick is absent or its observed count is <= 0, OCCUPIED when it is observed and its
+ *     f16 TSDF value, widened to f32, is < thres (the test of tsl_tsdf_query_points mode 0), FREE otherwise.  thres = free_thres, 0 = the map's surface
+ *     threshold 1.8 * voxel.  A voxel outside the volume has no class -- it is not unknown: the wall of the volume is no frontier.
+ *   Frontier voxel: a free voxel with at least min_unknown (1 .. 6, 0 = 1) of its six face neighbours unknown; with flags bit 0 none of its 26 neighbours
+ *     occupied (keeps targets off the grazing-angle holes next to surfaces); with k_min <= k_max also k_min <= k <= k_max (signed voxel indices; k_min >
+ *     k_max = no limit -- a zeroed cfg selects the layer k = 0).  mask: bit 0 .. 5 = the face neighbour at -x, +x, -y, +y, -z, +z is unknown.
+ *   Key of a voxel: ((ui * N) + uj) * Nz + uk, ui = i + N / 2, uj = j + N / 2, uk = k + Nz / 2.  The call is refused when N * N * Nz >= 2^31.
+ *   Clusters: the connected components of the frontier voxels under connectivity 6, 18 or 26 (0 = 26).  tsl_frontier_cluster (64 bytes): key = the least
+ *     voxel key of the cluster, count, sum = the int64 sums of i, j, k (centroid = sum / count * voxel), nsum[a] = the voxels whose +a neighbour is
+ *     unknown minus those whose -a neighbour is (the direction into the unknown), lo / hi = the bounding box.  Clusters with count < min_cluster (0 = 1)
+ *     are dropped, and so are their voxels.
+ *   Output: the voxels sorted by key -- idx int16 [n][3], mask u8 [n], cluster int32 [n] = the row of the voxel's cluster -- and the clusters sorted by key.
+ * tsl_tsdf_frontier_extract issues the queued frames, runs on the handle's stream behind them, waits, and returns the two counts; the result stays on
+ * the device (buffers that grow as needed: it is never truncated) until the next extraction.  tsl_tsdf_frontier_read copies the first n_voxels /
+ * n_clusters rows of it to the host (null pointers are skipped).  tsl_tsdf_frontier_dev runs the same pass after the work queued on `user_stream` and
+ * returns the device pointers of the result (null for an empty one; valid until the next extraction) and the counts; `user_stream` is made to wait for
+ * the result as with tsl_tsdf_render_view_dev.  The host waits for the counts, as tsl_mesh_buffers_dev does: they size the buffers.
+ * With profiling on, tsl_tsdf_prof_query returns the time of the stages: TSL_K_FRONTIER_MARK, _LABEL, _JOIN (join and flatten), _SUM (numbering the
+ * roots, the sums, the filter) and _EMIT (the two sorts and the output).
+ * TSL_ERR_ARG (the text names the entry point): a null handle / cfg, a free_thres that is not finite, a connectivity other than 0, 6, 18, 26, a
+ * min_unknown outside 0 .. 6, a negative min_cluster, a volume with N * N * Nz >= 2^31; frontier_read: no extraction yet, a negative size, more rows
+ * than the last extraction produced; frontier_dev: a null count pointer.  TSL_ERR_CAPACITY: an iteration cap of the labelling was reached.  The caps
+ * are true bounds of a well-formed parent array (a find: the node count, frontier bricks * 4096; a union: as many retries), so no map of any size reaches
+ * them; they only keep a kernel from spinning over corrupted memory.  A refused call leaves the handle usable. */
+typedef struct { float free_thres; int32_t k_min, k_max, min_unknown, connectivity, min_cluster, flags; } tsl_frontier_cfg;
+typedef struct { int32_t key, count; int64_t sum[3]; int32_t nsum[3]; int16_t lo[3], hi[3]; int32_t reserved_[2]; } tsl_frontier_cluster;
+int  tsl_tsdf_frontier_extract(tsl_tsdf* m, const tsl_frontier_cfg* cfg, int32_t* n_voxels, int32_t* n_clusters);
+int  tsl_tsdf_frontier_read(tsl_tsdf* m, int16_t* idx, uint8_t* mask, int32_t* cluster, tsl_frontier_cluster* clusters, int64_t n_voxels, int64_t n_clusters);
+int  tsl_tsdf_frontier_dev(tsl_tsdf* m, const tsl_frontier_cfg* cfg, void** idx_dev, void** mask_dev, void** cluster_dev, void** clusters_dev,
+                           int32_t* n_voxels, int32_t* n_clusters, void* user_stream);
 
 /* backend knobs for A/B-ing kernel variants: name in
      "variant"  0|1: one global int64 atomic pair per ray step, 2 (default): brick-binned LDS accumulation

@@ -7,9 +7,11 @@ from . import build as _build
 
 TSL_OK = 0
 K_VOXELIZE, K_SORT, K_RAYS, K_INTEGRATE, K_FINALIZE, K_MESH, K_SEGMENTS, K_BIN, K_ESDF, K_FUSE, K_REGISTER, K_REGISTER_SCORE = range(12)
+K_FRONTIER_MARK, K_FRONTIER_LABEL, K_FRONTIER_JOIN, K_FRONTIER_SUM, K_FRONTIER_EMIT = range(12, 17)
 KERNEL_NAMES = {K_VOXELIZE: "voxelize", K_SORT: "sort", K_RAYS: "build_rays", K_INTEGRATE: "integrate",
                 K_FINALIZE: "finalize", K_MESH: "marching_cubes", K_SEGMENTS: "segments", K_BIN: "bin", K_ESDF: "esdf", K_FUSE: "fuse", K_REGISTER: "register",
-                K_REGISTER_SCORE: "register_score"}
+                K_REGISTER_SCORE: "register_score", K_FRONTIER_MARK: "frontier_mark", K_FRONTIER_LABEL: "frontier_label", K_FRONTIER_JOIN: "frontier_join",
+                K_FRONTIER_SUM: "frontier_sum", K_FRONTIER_EMIT: "frontier_emit"}
 
 
 class TsdfCfg(C.Structure):
@@ -113,6 +115,19 @@ class SearchReport(C.Structure):
                 ("score_best", RegisterScore), ("pivot", C.c_double * 3), ("R_best", C.c_double * 9), ("T_best", C.c_double * 3), ("gate", RegisterGate)]
 
 
+class FrontierCfg(C.Structure):
+    """tsl_frontier_cfg (tsl_tsdf_frontier_extract): free_thres 0 = the map's surface threshold, k_min > k_max = no height limit, min_unknown /
+    connectivity / min_cluster 0 = 1 / 26 / 1, flags bit 0 = no occupied voxel among the 26 neighbours"""
+    _fields_ = [("free_thres", C.c_float), ("k_min", C.c_int32), ("k_max", C.c_int32), ("min_unknown", C.c_int32), ("connectivity", C.c_int32),
+                ("min_cluster", C.c_int32), ("flags", C.c_int32)]
+
+
+class FrontierCluster(C.Structure):
+    """tsl_frontier_cluster: 64 bytes, the layout of FRONTIER_CLUSTER_DTYPE"""
+    _fields_ = [("key", C.c_int32), ("count", C.c_int32), ("sum", C.c_int64 * 3), ("nsum", C.c_int32 * 3), ("lo", C.c_int16 * 3), ("hi", C.c_int16 * 3),
+                ("reserved_", C.c_int32 * 2)]
+
+
 class TslError(RuntimeError):
     pass
 
@@ -208,6 +223,9 @@ SIGNATURES = {
     "tsl_tsdf_register_score_tile": (C.c_int, [vp, i64, i32]),
     "tsl_tsdf_register_search": (C.c_int, [vp, C.c_int, vp, C.c_int, dp, dp, C.POINTER(RegisterCfg), C.POINTER(SearchCfg), C.POINTER(TrackCfg), dp, dp,
                                            C.POINTER(SearchReport), C.POINTER(TrackReport), C.POINTER(RegisterScore)]),
+    "tsl_tsdf_frontier_extract": (C.c_int, [vp, C.POINTER(FrontierCfg), pi32, pi32]),
+    "tsl_tsdf_frontier_read": (C.c_int, [vp, vp, vp, vp, vp, i64, i64]),
+    "tsl_tsdf_frontier_dev": (C.c_int, [vp, C.POINTER(FrontierCfg), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), pi32, pi32, vp]),
     "tsl_tsdf_set_option": (C.c_int, [vp, C.c_char_p, C.c_int]),
     "tsl_tsdf_get_option": (C.c_int, [vp, C.c_char_p, C.POINTER(C.c_int)]),
     "tsl_tsdf_prof_enable": (C.c_int, [vp, C.c_int]),

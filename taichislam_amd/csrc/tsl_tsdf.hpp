@@ -219,6 +219,8 @@ struct StageCopy { const uint4* src[2 * TSL_NB]; uint4* dst[2 * TSL_NB]; int n16
 int fuse_submaps_sequential(tsl_tsdf* g, tsl_tsdf* sub, const float* pose_dev, int nsrc);      // tsl_sequential.hip
 int esdf_finish(tsl_tsdf* m);            // tsl_esdf.hip: wait for the ESDF updates in flight (repairing one that stopped early)
 void esdf_release(tsl_tsdf* m);
+struct FrontierState;                    // tsl_frontier.hip: scratch and result of the frontier extraction
+void frontier_release(tsl_tsdf* m);
 }  // namespace tsl
 
 #define TSL_ESDF_SLOTS 4
@@ -284,6 +286,7 @@ struct tsl_tsdf {
     tsl::SeqDev seq_h[TSL_NSETS]; tsl::SeqDev* seq_d;      // seq_impl 1: tuple arrays of every working set (allocated by the first sequential batch)
     void *seqb_keys[TSL_NBATCH][2], *seqb_vals[TSL_NBATCH][2], *seqb_temp[TSL_NBATCH], *seqb_long[TSL_NBATCH], *seqb_lmask[TSL_NBATCH], *seqb_perm[TSL_NBATCH]; size_t seqb_temp_bytes; long long seq_tuple_cap;      // per batch slot: the rays' struct-for keys of all its frames, sorted in one call
     unsigned long long *seq_keys[2], *seq_vals[2], *seq_ctr; void* seq_temp; size_t seq_temp_bytes; long long seq_cap;
+    tsl::FrontierState* frontier;        // tsl_frontier.hip (allocated by the first extraction)
     int variant, split, phases, wg, spt, ncu, chunks, unit_max, unit_half, unit_floor, bgrid, ugrid, pgrid, split_launch, adaptive, ramp, ramp_batches, ramp_size; bool clean; uint64_t batch_gen;
     int64_t bytes;
     void* seqv_sum[TSL_NBATCH]; int* seqv_log;      // TSL_SEQ_VERIFY (developer aid, tsl_sequential.hip): per-item checksums, mismatch log

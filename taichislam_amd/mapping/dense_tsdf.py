@@ -174,6 +174,22 @@ def _half_counts(window, step):
     return counts, steps
 
 
+# tsl_frontier_cluster (include/taichislam_hip.h): 64 bytes at fixed offsets
+FRONTIER_CLUSTER_DTYPE = np.dtype({"names": ["key", "count", "sum", "nsum", "lo", "hi"],
+                                   "formats": [np.int32, np.int32, (np.int64, 3), (np.int32, 3), (np.int16, 3), (np.int16, 3)],
+                                   "offsets": [0, 4, 8, 32, 44, 50], "itemsize": 64})
+
+
+def frontier_cluster_geometry(clusters, voxel_scale):
+    """(centroid f64 [m, 3] in metres, unit normal f64 [m, 3] pointing into the unknown; 0 where the signed face counts cancel) of frontier cluster records"""
+    cnt = np.maximum(clusters["count"].astype(np.float64), 1.0)[:, None]
+    centroid = clusters["sum"].astype(np.float64) / cnt * float(voxel_scale)
+    ns = clusters["nsum"].astype(np.float64)
+    ln = np.sqrt((ns * ns).sum(1))[:, None]
+    normal = np.divide(ns, ln, out=np.zeros_like(ns), where=ln > 0)
+    return centroid.reshape(-1, 3), normal.reshape(-1, 3)
+
+
 def _depth_image(depth):
     """(pointer, (h, w), keep-alive, is_device) of a uint16 millimetre image: a numpy array or a torch CUDA tensor, the forms recast_depth_to_map accepts"""
     if _is_device_tensor(depth):
@@ -722,6 +738,66 @@ class DenseTSDF(BaseMap):
         status = np.empty((h, w), np.uint8)
         _lib.check(self.L.tsl_tsdf_render_view(self.h, r, t, C.byref(cfg), _vp(depth), _vp(normal), _vp(rgb), _vp(status)))
         return depth, normal, rgb, status
+
+    # ---- exploration frontiers (tsl_frontier.hip) ---------------------------------------------------
+    def extract_frontiers(self, free_thres=None, z_range=None, min_unknown=1, connectivity=26, min_cluster=1, clear_of_occupied=False, device=False):
+        """Where the known map ends: the free voxels of the submap the point queries read (the active one; submap 0 on a global map) that have at
+        least `min_unknown` of their six face neighbours unknown, grouped into connected clusters (connectivity 6, 18 or 26) -- the targets of an
+        exploration planner.  A voxel is unknown when its brick is absent or it was never observed, occupied when its TSDF is below `free_thres`
+        (default: the surface threshold of is_pos_occupy), free otherwise; the space outside the volume is not unknown.  z_range = (z0, z1) in metres
+        keeps the voxel layers with z0 <= k * voxel <= z1; clear_of_occupied drops voxels with an occupied voxel among their 26 neighbours; clusters
+        of fewer than min_cluster voxels are dropped with their voxels.  Returns a dict: `indices` int16 [n, 3], `xyz` f32 [n, 3] = indices * voxel
+        (the frame of is_pos_occupy), `mask` u8 [n] (bit 0 .. 5: the neighbour at -x, +x, -y, +y, -z, +z is unknown), `cluster` int32 [n] (row of
+        `clusters`), voxels sorted by key ((i + N / 2) * N + j + N / 2) * Nz + k + Nz / 2; `clusters`, a structured array (FRONTIER_CLUSTER_DTYPE:
+        key = least voxel key, count, sum int64 [3], nsum int32 [3], lo / hi int16 [3]) sorted by key; `centroid` f64 [m, 3] = sum / count * voxel
+        and `normal` f64 [m, 3] = nsum / |nsum| (0 where nsum is 0), the direction from the cluster into the unknown.  device=True returns indices,
+        xyz, mask and cluster as torch tensors on the map's device -- zero-copy views of the handle's result buffers, valid until the next call, ordered
+        with torch.cuda.current_stream -- and `clusters_dev`, the records as int32 [m, 16]; clusters, centroid and normal stay numpy (they are small)."""
+        cfg = _lib.FrontierCfg()
+        cfg.free_thres = 0.0 if free_thres is None else float(free_thres)
+        if free_thres is not None and not float(free_thres) > 0.0:
+            raise ValueError("extract_frontiers: free_thres must be positive")
+        cfg.k_min, cfg.k_max = 1, 0                                      # no height limit
+        if z_range is not None:
+            z0, z1 = float(z_range[0]), float(z_range[1])
+            if not (math.isfinite(z0) and math.isfinite(z1)):
+                raise ValueError("extract_frontiers: z_range is not finite")
+            k0 = max(-32768, min(32767, math.ceil(z0 / float(self.voxel_scale))))
+            k1 = max(-32768, min(32767, math.floor(z1 / float(self.voxel_scale))))
+            if k0 > k1:
+                raise ValueError("extract_frontiers: z_range holds no voxel layer")
+            cfg.k_min, cfg.k_max = k0, k1
+        cfg.min_unknown, cfg.connectivity, cfg.min_cluster = int(min_unknown), int(connectivity), int(min_cluster)
+        cfg.flags = 1 if clear_of_occupied else 0
+        nv, nc = C.c_int32(), C.c_int32()
+        vs = np.float32(self.voxel_scale)
+        if device:
+            torch = _torch()
+            from .fields import device_view
+            dev = torch.device(f"cuda:{self.device}")
+            p = [C.c_void_p() for _ in range(4)]
+            _lib.check(self.L.tsl_tsdf_frontier_dev(self.h, C.byref(cfg), C.byref(p[0]), C.byref(p[1]), C.byref(p[2]), C.byref(p[3]), C.byref(nv), C.byref(nc),
+                                                    torch.cuda.current_stream(dev).cuda_stream))
+            n, m = nv.value, nc.value
+            if n:
+                idx = device_view(p[0].value, (n, 3), "<i2", self, self.device); mask = device_view(p[1].value, (n,), "|u1", self, self.device)
+                cl = device_view(p[2].value, (n,), "<i4", self, self.device); cdev = device_view(p[3].value, (m, 16), "<i4", self, self.device)
+            else:
+                idx = torch.empty((0, 3), dtype=torch.int16, device=dev); mask = torch.empty(0, dtype=torch.uint8, device=dev)
+                cl = torch.empty(0, dtype=torch.int32, device=dev); cdev = torch.empty((0, 16), dtype=torch.int32, device=dev)
+            out = {"indices": idx, "xyz": idx.float() * float(vs), "mask": mask, "cluster": cl, "clusters_dev": cdev}
+            clusters = np.zeros(m, FRONTIER_CLUSTER_DTYPE)
+            _lib.check(self.L.tsl_tsdf_frontier_read(self.h, None, None, None, _vp(clusters), 0, m))
+        else:
+            _lib.check(self.L.tsl_tsdf_frontier_extract(self.h, C.byref(cfg), C.byref(nv), C.byref(nc)))
+            n, m = nv.value, nc.value
+            idx = np.zeros((n, 3), np.int16); mask = np.zeros(n, np.uint8); cl = np.zeros(n, np.int32)
+            clusters = np.zeros(m, FRONTIER_CLUSTER_DTYPE)
+            _lib.check(self.L.tsl_tsdf_frontier_read(self.h, _vp(idx), _vp(mask), _vp(cl), _vp(clusters), n, m))
+            out = {"indices": idx, "xyz": idx.astype(np.float32) * vs, "mask": mask, "cluster": cl}
+        out["clusters"] = clusters
+        out["centroid"], out["normal"] = frontier_cluster_geometry(clusters, float(self.voxel_scale))
+        return out
 
     # ---- frame-to-model alignment (tsl_align.hip, DESIGN.md section 4.8) ---------------------------------------------------
     def align_linearize(self, depth, R, T, K=None, stride=1, d_min=None, d_max=None, r_max=None, g_max=None, huber=0.0, device=False, counts_only=False):
