@@ -15,14 +15,16 @@
 // Every product x is added as the integer rint(x * 2^20) (round half to even) into int64 sums: integer sums do not depend on the order of
 // the additions, so the 33 integers are the same for any schedule.
 //
+// Buckets unknown to used, the products and their reduction are tsl_align_common.hpp's (al_sample, al_products, al_flush), shared with
+// tsl_register.hip and tsl_register_search.hip; the pixel gate, the back-projection and the tiling are this file's.
+//
 // One lane per visited pixel, a wave covers an 8 x 8 tile of them and a workgroup 16 x 16 (the tiling of k_render_view).  The 28 sums are reduced in
 // the wave by a halving butterfly -- at the step over lane bit b a lane keeps one half of its values and hands the other half to its partner, 16 + 8
 // + 4 + 2 + 1 + 1 = 32 exchanges instead of 28 x 6 -- the five counts by ballots, then across the four waves through LDS; one 64-bit integer
 // atomic per non-zero sum per workgroup.  No float atomics.  flags bit 0 leaves the products and their reduction out (H, b, e = 0, the counts as
 // usual): what the gathers cost alone (tools/bench_track.py).
 #include <cmath>
-#include "tsl_interp.hpp"
-#include "tsl_align_common.hpp"      // al_fix, al_halve, the step, the retraction and the iteration: shared with tsl_register.hip
+#include "tsl_align_common.hpp"      // the sampler, the products, the reduction, the step, the retraction and the iteration: shared with tsl_register.hip
 
 namespace tsl {
 
@@ -37,13 +39,10 @@ struct AlignDev {
 
 __global__ void __launch_bounds__(256) k_align_linearize(MapDev M, int s, AlignDev A, const uint16_t* __restrict__ depth, long long* __restrict__ acc)
 {
-    __shared__ long long sm[4][32];
-    __shared__ int sc[4][8];
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const int ii = blockIdx.x * 16 + (wave & 1) * 8 + (lane & 7), jj = blockIdx.y * 16 + (wave >> 1) * 8 + (lane >> 3);
-    const int* __restrict__ T = M.table + (size_t)s * M.nb3;
     int bucket = -1;                                              // not a visited pixel
-    float sv = 0.0f, g0 = 0.0f, g1 = 0.0f, g2 = 0.0f, p[3] = { 0.0f, 0.0f, 0.0f };
+    float sv = 0.0f, g[3] = { 0.0f, 0.0f, 0.0f }, p[3] = { 0.0f, 0.0f, 0.0f };
     if (ii < A.ww && jj < A.hh) {
         const int i = ii * A.stride, j = jj * A.stride;
         const uint16_t d = depth[(size_t)j * A.w + i];
@@ -52,22 +51,9 @@ __global__ void __launch_bounds__(256) k_align_linearize(MapDev M, int s, AlignD
         if (d != 0 && !(df > A.thr_max) && !(df < A.thr_min)) {
             const float dep = df / 1000.0f;
             const float px = ((float)i - A.cx) * dep / A.fx, py = ((float)j - A.cy) * dep / A.fy, pz = dep;
-            float u[3]; int b[3];
 #pragma unroll
-            for (int a = 0; a < 3; ++a) {
-                p[a] = ((A.R[a * 3] * px + A.R[a * 3 + 1] * py) + A.R[a * 3 + 2] * pz) + A.T[a];
-                u[a] = p[a] / A.vs; b[a] = cell_floor(u[a]);
-            }
-            bucket = AL_UNKNOWN;
-            float V[8];
-            if (isfinite(p[0]) && isfinite(p[1]) && isfinite(p[2]) && tsdf_read_cell(M, T, b[0], b[1], b[2], V)) {
-                const float f0 = u[0] - (float)b[0], f1 = u[1] - (float)b[1], f2 = u[2] - (float)b[2];
-                sv = tri_value(V, f0, f1, f2);
-                tri_grad(V, f0, f1, f2, &g0, &g1, &g2);
-                g0 = g0 / A.vs; g1 = g1 / A.vs; g2 = g2 / A.vs;
-                const float gg = (g0 * g0 + g1 * g1) + g2 * g2;
-                bucket = fabsf(sv) > A.r_max ? AL_FAR : (gg == 0.0f || gg > A.gm2) ? AL_GRAD : AL_USED;
-            }
+            for (int a = 0; a < 3; ++a) p[a] = ((A.R[a * 3] * px + A.R[a * 3 + 1] * py) + A.R[a * 3 + 2] * pz) + A.T[a];
+            bucket = al_sample(p, M, M.table + (size_t)s * M.nb3, A.vs, A.r_max, A.gm2, &sv, g);
         }
     }
     const bool used = bucket == AL_USED;
@@ -75,39 +61,10 @@ __global__ void __launch_bounds__(256) k_align_linearize(MapDev M, int s, AlignD
 #pragma unroll
     for (int k = 0; k < 32; ++k) v[k] = 0;
     const bool sums = !(A.flags & 1);                             // the A/B switch: without the products and their reduction only the counts are formed
-    if (used && sums) {
-        const float J[6] = { g0, g1, g2, p[1] * g2 - p[2] * g1, p[2] * g0 - p[0] * g2, p[0] * g1 - p[1] * g0 };
-        const float as = fabsf(sv);
-        const float wgt = (A.huber > 0.0f && as > A.huber) ? A.huber / as : 1.0f;
-        float wJ[6];
-#pragma unroll
-        for (int a = 0; a < 6; ++a) wJ[a] = wgt * J[a];
-        int k = 0;
-#pragma unroll
-        for (int a = 0; a < 6; ++a)
-#pragma unroll
-            for (int c = a; c < 6; ++c) v[k++] = al_fix(wJ[a] * J[c]);
-#pragma unroll
-        for (int a = 0; a < 6; ++a) v[21 + a] = al_fix(wJ[a] * sv);
-        v[27] = al_fix((wgt * sv) * sv);
-    }
-    // the wave's sums: after the five halving steps lane l holds sum number l >> 1 over its half of the wave, the last step adds the other half
+    if (used && sums) al_products(p, g, sv, A.huber, v);           // the residual is the distance itself
     const unsigned long long mu = __ballot(used);
-    if (mu && sums) {
-        al_halve<32, 32>(v, lane); al_halve<16, 16>(v, lane); al_halve<8, 8>(v, lane); al_halve<4, 4>(v, lane); al_halve<2, 2>(v, lane);
-        v[0] += __shfl_xor(v[0], 1);
-    }
-    if (!(lane & 1)) sm[wave][lane >> 1] = v[0];
-    const unsigned long long mg = __ballot(bucket == AL_GATE), mk = __ballot(bucket == AL_UNKNOWN), mf = __ballot(bucket == AL_FAR), mr = __ballot(bucket == AL_GRAD);
-    if (lane == 0) { sc[wave][AL_USED] = popc64(mu); sc[wave][AL_GATE] = popc64(mg); sc[wave][AL_UNKNOWN] = popc64(mk); sc[wave][AL_FAR] = popc64(mf); sc[wave][AL_GRAD] = popc64(mr); }
-    __syncthreads();
-    const int t = threadIdx.x;
-    if (t < AL_NPROD + 5) {
-        long long sum;
-        if (t < AL_NPROD) sum = (sm[0][t] + sm[1][t]) + (sm[2][t] + sm[3][t]);
-        else { const int c = t - AL_NPROD; sum = (long long)((sc[0][c] + sc[1][c]) + (sc[2][c] + sc[3][c])); }
-        if (sum != 0) __hip_atomic_fetch_add(acc + t, sum, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
+    al_flush(v, popc64(mu), popc64(__ballot(bucket == AL_GATE)), popc64(__ballot(bucket == AL_UNKNOWN)), popc64(__ballot(bucket == AL_FAR)),
+             popc64(__ballot(bucket == AL_GRAD)), mu && sums, acc);
 }
 
 // the checks and defaults every form shares; `stride` replaces the configuration's (the levels of the tracker)
@@ -164,10 +121,7 @@ static int align_launch(tsl_tsdf* m, hipStream_t q, const AlignDev& A, const uin
 static int align_run(tsl_tsdf* m, hipStream_t q, const AlignDev& A, const uint16_t* depth_dev, long long* acc, tsl_align_sums* out)
 {
     int rc = align_launch(m, q, A, depth_dev, acc); if (rc) return rc;
-    TSL_HIP(hipMemcpyAsync(al_pinned(m), acc, sizeof(tsl_align_sums), hipMemcpyDeviceToHost, q));
-    TSL_HIP(hipStreamSynchronize(q));
-    std::memcpy(out, al_pinned(m), sizeof(tsl_align_sums));
-    return TSL_OK;
+    return al_read_back(m, q, acc, sizeof(tsl_align_sums), out);
 }
 
 // the accumulator and (host form) the staged image in the export staging buffer: [40 x int64 | pad to 512 | depth]

@@ -1,10 +1,12 @@
-// tsl_align_common.hpp -- what the two Gauss-Newton linearisations share: the frame-to-model alignment (tsl_align.hip) and the
-// map-to-map registration (tsl_register.hip, section 4.9).  Device side: the 2^-20 fixed-point conversion and the halving butterfly of the wave
-// reduction.  Host side: the float64 step and the Cayley retraction in their fixed order (tests/track_ref.py restates both), the checks of a
-// tsl_track_cfg and the iteration over its levels.  One copy, so that both kernels and both loops compute the same thing.
+// tsl_align_common.hpp -- the one copy of what the Gauss-Newton family shares: the frame-to-model alignment (tsl_align.hip), the
+// map-to-map registration (tsl_register.hip, section 4.9) and the pose scoring (tsl_register_search.hip, section 4.10).  Device side, the bit-exact
+// contract that tests/track_ref.py restates (points, robust_weight): al_sample carries a map-frame point into its bucket, al_weight is the robust
+// weight, al_products adds the 28 fixed-point products of a used sample, al_flush reduces them over the workgroup (the halving butterfly, LDS, one
+// integer atomic per non-zero sum).  Host side: the float64 step and the Cayley retraction in their fixed order (tests/track_ref.py restates both),
+// the checks of a tsl_track_cfg, the iteration over its levels and the copy of a result through the pinned buffer.
 #pragma once
 #include <cmath>
-#include "tsl_tsdf.hpp"
+#include "tsl_interp.hpp"
 
 namespace tsl {
 
@@ -38,9 +40,85 @@ __device__ __forceinline__ void al_halve(long long (&v)[32], int lane)
     }
 }
 
+// The bucket of the sample at the map-frame point p -- AL_UNKNOWN, AL_FAR, AL_GRAD or AL_USED -- and, for a used one, the interpolant *s and its
+// gradient g per metre.  T: the table of the map's submap; gm2 = g_max * g_max.  The f32 expressions and their order are the contract.
+__device__ __forceinline__ int al_sample(const float p[3], const MapDev& M, const int* __restrict__ T, float vs, float r_max, float gm2, float* s, float g[3])
+{
+    float u[3]; int b[3];
+#pragma unroll
+    for (int a = 0; a < 3; ++a) { u[a] = p[a] / vs; b[a] = cell_floor(u[a]); }
+    float V[8];
+    if (!(isfinite(p[0]) && isfinite(p[1]) && isfinite(p[2]) && tsdf_read_cell(M, T, b[0], b[1], b[2], V))) return AL_UNKNOWN;
+    const float f0 = u[0] - (float)b[0], f1 = u[1] - (float)b[1], f2 = u[2] - (float)b[2];
+    *s = tri_value(V, f0, f1, f2);
+    if (fabsf(*s) > r_max) return AL_FAR;
+    tri_grad(V, f0, f1, f2, &g[0], &g[1], &g[2]);
+    g[0] = g[0] / vs; g[1] = g[1] / vs; g[2] = g[2] / vs;
+    const float gg = (g[0] * g[0] + g[1] * g[1]) + g[2] * g[2];
+    return (gg == 0.0f || gg > gm2) ? AL_GRAD : AL_USED;
+}
+
+// the robust weight of the residual r
+__device__ __forceinline__ float al_weight(float r, float huber)
+{
+    const float ar = fabsf(r);
+    return (huber > 0.0f && ar > huber) ? huber / ar : 1.0f;
+}
+
+// adds the 28 products of a used sample to v: H_ab = wJ[a] J[b] (a <= b) in v[0 .. 20], b_a = wJ[a] r in v[21 .. 26], e = (wgt r) r in v[27]
+__device__ __forceinline__ void al_products(const float p[3], const float g[3], float r, float huber, long long (&v)[32])
+{
+    const float J[6] = { g[0], g[1], g[2], p[1] * g[2] - p[2] * g[1], p[2] * g[0] - p[0] * g[2], p[0] * g[1] - p[1] * g[0] };
+    const float wgt = al_weight(r, huber);
+    float wJ[6];
+#pragma unroll
+    for (int a = 0; a < 6; ++a) wJ[a] = wgt * J[a];
+    int k = 0;
+#pragma unroll
+    for (int a = 0; a < 6; ++a)
+#pragma unroll
+        for (int c = a; c < 6; ++c) v[k++] += al_fix(wJ[a] * J[c]);
+#pragma unroll
+    for (int a = 0; a < 6; ++a) v[21 + a] += al_fix(wJ[a] * r);
+    v[27] += al_fix((wgt * r) * r);
+}
+
+// The end of a linearisation kernel of 256 threads: the sums v of every lane and the five counts of every wave (uniform in the wave) are added into
+// acc[0 .. 32].  reduce: some lane of this wave holds products (it used a sample and the sums are wanted); otherwise v is zero and the butterfly is
+// left out.  After the five halving steps lane l holds sum number l >> 1 over its half of the wave, the last step adds the other half.
+__device__ __forceinline__ void al_flush(long long (&v)[32], int n_used, int n_gate, int n_unknown, int n_far, int n_grad, bool reduce, long long* __restrict__ acc)
+{
+    __shared__ long long sm[4][32];
+    __shared__ int sc[4][8];
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    if (reduce) {
+        al_halve<32, 32>(v, lane); al_halve<16, 16>(v, lane); al_halve<8, 8>(v, lane); al_halve<4, 4>(v, lane); al_halve<2, 2>(v, lane);
+        v[0] += __shfl_xor(v[0], 1);
+    }
+    if (!(lane & 1)) sm[wave][lane >> 1] = v[0];
+    if (lane == 0) { sc[wave][AL_USED] = n_used; sc[wave][AL_GATE] = n_gate; sc[wave][AL_UNKNOWN] = n_unknown; sc[wave][AL_FAR] = n_far; sc[wave][AL_GRAD] = n_grad; }
+    __syncthreads();
+    const int t = threadIdx.x;
+    if (t < AL_NPROD + 5) {
+        long long sum;
+        if (t < AL_NPROD) sum = (sm[0][t] + sm[1][t]) + (sm[2][t] + sm[3][t]);
+        else { const int c = t - AL_NPROD; sum = ((long long)sc[0][c] + sc[1][c]) + ((long long)sc[2][c] + sc[3][c]); }      // widened before the additions
+        if (sum != 0) __hip_atomic_fetch_add(acc + t, sum, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+}
+
 static bool al_finite(const double* a, int n) { for (int i = 0; i < n; ++i) if (!std::isfinite(a[i])) return false; return true; }
 
 static long long* al_pinned(tsl_tsdf* m) { return reinterpret_cast<long long*>(m->h_ints + 128); }      // the upper part of the pinned scratch: 40 x int64
+
+// `bytes` (at most 40 x int64) at `dev` to `out` on the host: through the pinned buffer on q; q is idle when it returns
+static int al_read_back(tsl_tsdf* m, hipStream_t q, const void* dev, size_t bytes, void* out)
+{
+    TSL_HIP(hipMemcpyAsync(al_pinned(m), dev, bytes, hipMemcpyDeviceToHost, q));
+    TSL_HIP(hipStreamSynchronize(q));
+    std::memcpy(out, al_pinned(m), bytes);
+    return TSL_OK;
+}
 
 // ---- the step and the retraction: host code, float64, in this order (tests/track_ref.py restates both) ----
 

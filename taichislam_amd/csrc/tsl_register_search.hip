@@ -6,7 +6,8 @@
 // Definition (tests/register_search_ref.py restates it in numpy and every integer must equal it).  The score of pose k is
 // e, n_used, n_unknown, n_far and n_grad of the tsl_align_sums that tsl_tsdf_register_linearize returns for that pose with the same handles, submap
 // ids and configuration (section 4.9): the same lattice, gates, buckets, robust weight, f32 rounding of the pose and f32 order of evaluation.  The
-// gradient is formed because n_grad depends on it; the 27 products of H and b are not.
+// gradient is formed because n_grad depends on it (not for a far sample: al_sample returns before it); the 27 products of H and b are not.  The gather
+// is pass 1 of tsl_register_common.hpp, the sample and the weight are al_sample and al_weight of tsl_align_common.hpp: the code of the linearisation.
 //
 // Kernels.  What does not depend on the pose is done once per call:
 //   k_score_gather, counting   one workgroup per source brick, pass 1 of k_register_linearize (16-byte row loads, the lattice, weight and band tests,
@@ -23,7 +24,6 @@
 #include <cmath>
 #include <memory>
 #include <vector>
-#include "tsl_interp.hpp"
 #include "tsl_align_common.hpp"
 #include "tsl_register_common.hpp"
 
@@ -37,8 +37,8 @@ namespace tsl {
 
 static size_t sc_align(size_t b) { return (b + 255) & ~(size_t)255; }
 
-// Pass 1 of k_register_linearize over the bricks of submap `ss`.  list == nullptr: count (ctr[0..4]).  Otherwise append the survivors to `list`,
-// ctr[5] the cursor; `cap` = the n_pass a counting launch found on the same map, so no entry can land past it.
+// Pass 1 of k_register_linearize (rg_brick_origin, rg_scan_row, rg_push) over the bricks of submap `ss`.  list == nullptr: count (ctr[0..4]).
+// Otherwise append the survivors to `list`, ctr[5] the cursor; `cap` = the n_pass a counting launch found on the same map, so no entry can land past it.
 __global__ void __launch_bounds__(256) k_score_gather(MapDev S, int ss, RegisterDev A, long long* __restrict__ ctr, uint2* __restrict__ list, long long cap)
 {
     __shared__ uint32_t queue[TSL_BRK3];
@@ -49,48 +49,24 @@ __global__ void __launch_bounds__(256) k_score_gather(MapDev S, int ss, Register
     const bool fill = list != nullptr;
     int top = *S.pool_top;
     if (top > S.max_bricks) top = S.max_bricks;
-    const int first = ss * S.nb3;
     long long n_gate = 0, n_pass = 0, si = 0, sj = 0, sk = 0;     // n_gate / n_pass per wave (uniform), the index sums per lane
-    const int li = threadIdx.x >> 4, lj = threadIdx.x & 15;       // the k-row this thread reads
 
     for (int pb = blockIdx.x; pb < top; pb += gridDim.x) {
-        const int b = S.owner[pb] - first;                        // uniform: the whole workgroup skips a brick of another submap
-        if (b < 0 || b >= S.nb3) continue;
-        const int bk = b % S.nbz, bj = (b / S.nbz) % S.nbx, bi = b / (S.nbz * S.nbx);
-        const int i0 = bi * 16 - S.hN, j0 = bj * 16 - S.hN, k0 = bk * 16 - S.hNz;
+        int i0, j0, k0;
+        if (!rg_brick_origin(S, pb, ss * S.nb3, &i0, &j0, &k0)) continue;      // uniform: the whole workgroup skips a brick of another submap
         if (fill) {
             if (threadIdx.x == 0) q_n = 0;
             __syncthreads();
         }
-        const bool row = (((i0 + li) | (j0 + lj)) & A.smask) == 0;
-        uint4 ob = make_uint4(0u, 0u, 0u, 0u), t0 = ob, t1 = ob, t2 = ob, t3 = ob;
-        if (row) {
-            ob = *reinterpret_cast<const uint4*>(S.obs + (size_t)pb * TSL_BRK3 + threadIdx.x * 16);
-            const uint4* tp = reinterpret_cast<const uint4*>(S.tw + (size_t)pb * TSL_BRK3 + threadIdx.x * 16);
-            t0 = tp[0]; t1 = tp[1]; t2 = tp[2]; t3 = tp[3];
-        }
-        const uint32_t obw[4] = { ob.x, ob.y, ob.z, ob.w };
-        const uint32_t tww[16] = { t0.x, t0.y, t0.z, t0.w, t1.x, t1.y, t1.z, t1.w, t2.x, t2.y, t2.z, t2.w, t3.x, t3.y, t3.z, t3.w };
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            if ((k0 + r) & A.smask) continue;                     // uniform
-            const bool seen = row && (int8_t)((obw[r >> 2] >> ((r & 3) * 8)) & 0xffu) > 0;
-            const uint32_t tw = tww[r];
-            const float w = h2f((h16)(tw >> 16)), t = h2f((h16)(tw & 0xffffu));
-            const bool pass = seen && (w >= A.w_min) && !(fabsf(t) > A.band);
+        rg_scan_row(S, A, pb, i0, j0, k0, [&](int r, bool seen, bool pass, uint32_t tw) {
             const unsigned long long m = __ballot(pass);
-            if (!fill) {
+            if (fill) rg_push(m, pass, r, tw, &q_n, queue, 0);
+            else {
                 n_gate += popc64(__ballot(seen && !pass));
                 n_pass += popc64(m);
-                if (pass) { si += i0 + li; sj += j0 + lj; sk += k0 + r; }
-            } else if (m) {
-                const int leader = (int)__builtin_ctzll(m);
-                int base = 0;
-                if (lane == leader) base = atomicAdd(&q_n, popc64(m));
-                base = __shfl(base, leader);
-                if (pass) queue[base + rank_below(m)] = ((uint32_t)(threadIdx.x * 16 + r) << 16) | (tw & 0xffffu);      // at most 4096 per brick
+                if (pass) { si += i0 + (int)(threadIdx.x >> 4); sj += j0 + (int)(threadIdx.x & 15); sk += k0 + r; }
             }
-        }
+        });
         if (fill) {
             __syncthreads();
             const int n = q_n;
@@ -99,9 +75,9 @@ __global__ void __launch_bounds__(256) k_score_gather(MapDev S, int ss, Register
             const long long at = q_first;
             for (int e = threadIdx.x; e < n; e += 256) {
                 const uint32_t ent = queue[e];
-                const int l = (int)(ent >> 16);
-                const uint32_t i = (uint32_t)(i0 + (l >> 8)) & 0xffffu, j = (uint32_t)(j0 + ((l >> 4) & 15)) & 0xffffu, k = (uint32_t)(k0 + (l & 15)) & 0xffffu;
-                if (at + e < cap) list[at + e] = make_uint2(i | (j << 16), k | ((ent & 0xffffu) << 16));
+                int i, j, k;
+                rg_entry_voxel((int)(ent >> 16), i0, j0, k0, &i, &j, &k);
+                if (at + e < cap) list[at + e] = make_uint2(((uint32_t)i & 0xffffu) | (((uint32_t)j & 0xffffu) << 16), ((uint32_t)k & 0xffffu) | ((ent & 0xffffu) << 16));
             }
         }
     }
@@ -138,28 +114,15 @@ __global__ void __launch_bounds__(SC_POSES) k_register_score(MapDev D, int ds, R
         const uint2 en = ent[e];                                  // the same address in every lane: a broadcast
         const float tv = h2f((h16)(en.y >> 16));
         const float q0 = (float)(int)(short)(en.x & 0xffffu) * A.vs, q1 = (float)(int)(short)(en.x >> 16) * A.vs, q2 = (float)(int)(short)(en.y & 0xffffu) * A.vs;
-        float p[3], u[3]; int c[3];
+        float p[3], sv, g[3];
 #pragma unroll
-        for (int a = 0; a < 3; ++a) {
-            p[a] = ((R[a * 3] * q0 + R[a * 3 + 1] * q1) + R[a * 3 + 2] * q2) + T[a];
-            u[a] = p[a] / A.vs; c[a] = cell_floor(u[a]);
-        }
-        float V[8];
-        if (!(isfinite(p[0]) && isfinite(p[1]) && isfinite(p[2]) && tsdf_read_cell(D, Td, c[0], c[1], c[2], V))) { ++n_unknown; continue; }
-        const float f0 = u[0] - (float)c[0], f1 = u[1] - (float)c[1], f2 = u[2] - (float)c[2];
-        const float sv = tri_value(V, f0, f1, f2);
-        if (fabsf(sv) > A.r_max) { ++n_far; continue; }
-        float g0, g1, g2;
-        tri_grad(V, f0, f1, f2, &g0, &g1, &g2);
-        g0 = g0 / A.vs; g1 = g1 / A.vs; g2 = g2 / A.vs;
-        const float gg = (g0 * g0 + g1 * g1) + g2 * g2;
-        if (gg == 0.0f || gg > A.gm2) { ++n_grad; continue; }
+        for (int a = 0; a < 3; ++a) p[a] = ((R[a * 3] * q0 + R[a * 3 + 1] * q1) + R[a * 3 + 2] * q2) + T[a];
+        const int bucket = al_sample(p, D, Td, A.vs, A.r_max, A.gm2, &sv, g);
+        if (bucket == AL_UNKNOWN) { ++n_unknown; continue; }
+        if (bucket == AL_FAR) { ++n_far; continue; }
+        if (bucket == AL_GRAD) { ++n_grad; continue; }
         ++n_used;
-        if (sums) {
-            const float r = sv - tv, ar = fabsf(r);
-            const float wgt = (A.huber > 0.0f && ar > A.huber) ? A.huber / ar : 1.0f;
-            e_sum += al_fix((wgt * r) * r);
-        }
+        if (sums) { const float r = sv - tv; e_sum += al_fix((al_weight(r, A.huber) * r) * r); }
     }
     tsl_register_score* o = out + k;
     if (e_sum != 0) __hip_atomic_fetch_add((long long*)&o->e, e_sum, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -189,28 +152,15 @@ static int sc_tile(long long len, long long chunks, int ncu)
     return tile;
 }
 
-static int gather_grid(const tsl_tsdf* dst, const tsl_tsdf* src)
-{
-    int grid = src->M.max_bricks;                                  // never more workgroups than pool bricks
-    if (grid > 4 * dst->ncu) grid = 4 * dst->ncu;
-    return grid < 1 ? 1 : grid;
-}
-
 // The counting pass alone: what does not depend on the pose.  The stream is idle when it returns.
 static int gate_run(tsl_tsdf* dst, tsl_tsdf* src, int src_sid, const RegisterDev& A, tsl_register_gate* gate)
 {
-    TSL_HIP(hipSetDevice(dst->device));
-    if (src != dst) { const int rc = tsl_tsdf_sync(src); if (rc) return rc; }      // as tsl_tsdf_fuse_submaps: the source is complete before dst's stream reads it
-    hipStream_t q = ms(dst);
-    const int rc = grow(&dst->xbuf, &dst->xbuf_bytes, SC_POSE_OFF); if (rc) return rc;
-    long long* ctr = (long long*)dst->xbuf;
+    hipStream_t q; long long* ctr;
+    const int rc = register_stage(dst, src, SC_POSE_OFF, &q, &ctr); if (rc) return rc;
     TSL_HIP(hipMemsetAsync(ctr, 0, SC_CTR * sizeof(long long), q));
-    hipLaunchKernelGGL(k_score_gather, dim3((unsigned)gather_grid(dst, src)), dim3(256), 0, q, src->M, rg_slot(src, src_sid), A, ctr, (uint2*)nullptr, 0LL);
+    hipLaunchKernelGGL(k_score_gather, dim3((unsigned)rg_grid(dst, src)), dim3(256), 0, q, src->M, rg_slot(src, src_sid), A, ctr, (uint2*)nullptr, 0LL);
     TSL_HIP(hipGetLastError());
-    TSL_HIP(hipMemcpyAsync(al_pinned(dst), ctr, 5 * sizeof(long long), hipMemcpyDeviceToHost, q));
-    TSL_HIP(hipStreamSynchronize(q));
-    std::memcpy(gate, al_pinned(dst), sizeof(*gate));
-    return TSL_OK;
+    return al_read_back(dst, q, ctr, sizeof(*gate), gate);
 }
 
 static int score_run(tsl_tsdf* dst, int dst_sid, tsl_tsdf* src, int src_sid, const double* R, const double* T, int32_t n, const RegisterDev& A,
@@ -219,7 +169,7 @@ static int score_run(tsl_tsdf* dst, int dst_sid, tsl_tsdf* src, int src_sid, con
     tsl_register_gate g;
     int rc = gate_run(dst, src, src_sid, A, &g); if (rc) return rc;
     hipStream_t q = ms(dst);
-    const int grid = gather_grid(dst, src);
+    const int grid = rg_grid(dst, src);
     const int ss = rg_slot(src, src_sid), ds = rg_slot(dst, dst_sid);
     if (gate) *gate = g;
     std::memset(out, 0, sizeof(tsl_register_score) * (size_t)n);

@@ -140,6 +140,17 @@ def _track_config(levels, min_step, damping, min_used):
     return tc
 
 
+def _sid(sid):
+    """A submap id as the library takes it: -1 = the active submap"""
+    return -1 if sid is None else int(sid)
+
+
+def _pose_out():
+    """(R [9], T [3], their pointers): the float64 arrays a call writes its pose into"""
+    Ro, To = np.empty(9, np.float64), np.empty(3, np.float64)
+    return Ro, To, Ro.ctypes.data_as(_lib.dp), To.ctypes.data_as(_lib.dp)
+
+
 def _track_info(rep):
     """The info dict of track_depth / register_submap from a tsl_track_report"""
     records = []
@@ -840,9 +851,8 @@ class DenseTSDF(BaseMap):
         cfg = align_config(K, shape, 1, **gates)
         tc = _track_config(levels, min_step, damping, min_used)
         r, t = _dptr(R, 9)[1], _dptr(T, 3)[1]
-        Ro, To = np.empty(9, np.float64), np.empty(3, np.float64)
+        Ro, To, ro, to = _pose_out()
         rep = _lib.TrackReport()
-        ro, to = Ro.ctypes.data_as(_lib.dp), To.ctypes.data_as(_lib.dp)
         if on_dev:
             torch = _torch()
             _lib.check(self.L.tsl_tsdf_track_depth_dev(self.h, r, t, C.byref(cfg), C.byref(tc), ptr, ro, to, C.byref(rep),
@@ -863,7 +873,7 @@ class DenseTSDF(BaseMap):
         A/B switch of tools/bench_register.py)."""
         cfg = register_config(stride, w_min, band, r_max, g_max, huber, counts_only)
         sums = _lib.AlignSums()
-        _lib.check(self.L.tsl_tsdf_register_linearize(self.h, -1 if dst_sid is None else int(dst_sid), src.h, -1 if src_sid is None else int(src_sid),
+        _lib.check(self.L.tsl_tsdf_register_linearize(self.h, _sid(dst_sid), src.h, _sid(src_sid),
                                                       _dptr(R, 9)[1], _dptr(T, 3)[1], C.byref(cfg), C.byref(sums)))
         return align_sums_dict(np.frombuffer(sums, dtype=np.int64))
 
@@ -877,11 +887,10 @@ class DenseTSDF(BaseMap):
         constraint.  w_min / band / r_max / g_max / huber: the gates of register_linearize."""
         cfg = register_config(1, w_min, band, r_max, g_max, huber)
         tc = _track_config(REGISTER_LEVELS if levels is None else levels, min_step, damping, min_used)
-        Ro, To = np.empty(9, np.float64), np.empty(3, np.float64)
+        Ro, To, ro, to = _pose_out()
         rep = _lib.TrackReport()
-        _lib.check(self.L.tsl_tsdf_register_submap(self.h, -1 if dst_sid is None else int(dst_sid), src.h, -1 if src_sid is None else int(src_sid),
-                                                   _dptr(R0, 9)[1], _dptr(T0, 3)[1], C.byref(cfg), C.byref(tc), Ro.ctypes.data_as(_lib.dp),
-                                                   To.ctypes.data_as(_lib.dp), C.byref(rep)))
+        _lib.check(self.L.tsl_tsdf_register_submap(self.h, _sid(dst_sid), src.h, _sid(src_sid), _dptr(R0, 9)[1], _dptr(T0, 3)[1], C.byref(cfg), C.byref(tc), ro, to,
+                                                   C.byref(rep)))
         return Ro.reshape(3, 3), To, _track_info(rep)
 
     # ---- pose search for the registration (tsl_register_search.hip, DESIGN.md section 4.10) -------------------------------
@@ -899,7 +908,7 @@ class DenseTSDF(BaseMap):
         cfg = register_config(stride, w_min, band, r_max, g_max, huber, counts_only)
         out = np.zeros(max(n, 1), _SCORE_DTYPE)
         gate = _lib.RegisterGate()
-        _lib.check(self.L.tsl_tsdf_register_score(self.h, -1 if dst_sid is None else int(dst_sid), src.h, -1 if src_sid is None else int(src_sid),
+        _lib.check(self.L.tsl_tsdf_register_score(self.h, _sid(dst_sid), src.h, _sid(src_sid),
                                                   R.ctypes.data_as(_lib.dp), T.ctypes.data_as(_lib.dp), n, C.byref(cfg),
                                                   out.ctypes.data_as(C.POINTER(_lib.RegisterScore)), C.byref(gate)))
         return dict(_scores_dict(out[:n]), gate=gate.as_dict())
@@ -937,11 +946,10 @@ class DenseTSDF(BaseMap):
         for v in nr + nt:
             total *= 2 * max(v, 0) + 1
         scores = np.zeros(total, _SCORE_DTYPE) if return_scores and total <= 65536 else None
-        Ro, To = np.empty(9, np.float64), np.empty(3, np.float64)
+        Ro, To, ro, to = _pose_out()
         rep, trk = _lib.SearchReport(), _lib.TrackReport()
-        _lib.check(self.L.tsl_tsdf_register_search(self.h, -1 if dst_sid is None else int(dst_sid), src.h, -1 if src_sid is None else int(src_sid),
-                                                   _dptr(R0, 9)[1], _dptr(T0, 3)[1], C.byref(cfg), C.byref(sc), C.byref(tc), Ro.ctypes.data_as(_lib.dp),
-                                                   To.ctypes.data_as(_lib.dp), C.byref(rep), C.byref(trk),
+        _lib.check(self.L.tsl_tsdf_register_search(self.h, _sid(dst_sid), src.h, _sid(src_sid), _dptr(R0, 9)[1], _dptr(T0, 3)[1], C.byref(cfg), C.byref(sc), C.byref(tc),
+                                                   ro, to, C.byref(rep), C.byref(trk),
                                                    None if scores is None else scores.ctypes.data_as(C.POINTER(_lib.RegisterScore))))
         info = _track_info(trk)
         sb = rep.score_best

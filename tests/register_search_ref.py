@@ -73,10 +73,7 @@ def score(src, R, T, stride, vs, grid, w_min, band, r_max, g_max, huber=0.0, cou
             bad = kn & ~far & ((gg == 0) | (gg > gm2))
             used = kn & ~far & ~bad
             r = (s - np.tile(t, c)).astype(F32)
-            a_r = np.abs(r)
-            one = np.ones_like(r)
-            wgt = np.where((huber > 0) & (a_r > huber), huber / np.where(a_r > 0, a_r, one), one).astype(F32)
-            e = np.where(used, tr.fix((wgt * r) * r), 0)
+            e = np.where(used, tr.fix((tr.robust_weight(r, huber) * r) * r), 0)
             sl = slice(a0, a0 + c)
             out["e"][sl] = e.reshape(c, m).sum(1)
             out["n_used"][sl] = used.reshape(c, m).sum(1)

@@ -1,6 +1,7 @@
 """numpy restatement of the frame-to-model alignment (taichislam_amd/csrc/tsl_align.hip).  linearize: float32 in the written
 order, the 33 integers of tsl_align_sums, which the GPU must equal.  solve / retract / track: float64 scalar code in the written order, which the
-library's host functions must equal bit for bit.  The map is a dense grid as in render_view_ref: val / known [N][N][Nz] indexed by voxel index - lo."""
+library's host functions must equal bit for bit.  points, robust_weight and iterate are what the registration (tests/register_ref.py) and the pose
+search (tests/register_search_ref.py) share with it, as the kernels share tsl_align_common.hpp.  The map is a dense grid as in render_view_ref: val / known [N][N][Nz] indexed by voxel index - lo."""
 import math
 
 import numpy as np
@@ -23,11 +24,56 @@ def fix(x):
     return np.rint(np.asarray(x, F32).astype(np.float64) * SCALE).astype(np.int64)
 
 
+def robust_weight(r, huber):
+    """wgt = huber > 0 && |r| > huber ? huber / |r| : 1 in f32"""
+    a_r = np.abs(r)
+    one = np.ones_like(r)
+    return np.where((huber > 0) & (a_r > huber), huber / np.where(a_r > 0, a_r, one), one).astype(F32)
+
+
+def points(p, t, vs, grid, r_max, g_max, huber, n_gate=0):
+    """What the alignment and the registration share: the 33 integers of the map-frame points p f32 [n, 3] against the target values t f32 [n] (zeros
+    for the alignment): each point is unknown, far, grad or used, a used one adds its 28 products with the residual r = s - t.  n_gate: the
+    caller's gate count, which it formed on the way to p."""
+    val, known, lo = grid
+    vs, r_max, g_max, huber = F32(vs), F32(r_max), F32(g_max), F32(huber)
+    gm2 = g_max * g_max
+    out = np.zeros(N_SUMS, np.int64)
+    out[I_GATE] = n_gate
+    with np.errstate(invalid="ignore", over="ignore", divide="ignore"):
+        s, kn, g = rv.sample(p, vs, val, known, lo)
+        out[I_UNKNOWN] = (~kn).sum()
+        p, s, t, g = p[kn], s[kn], t[kn], (g[kn] / vs).astype(F32)
+        far = np.abs(s) > r_max
+        out[I_FAR] = far.sum()
+        p, s, t, g = p[~far], s[~far], t[~far], g[~far]
+        gg = (g[:, 0] * g[:, 0] + g[:, 1] * g[:, 1]) + g[:, 2] * g[:, 2]
+        bad = (gg == 0) | (gg > gm2)
+        out[I_GRAD] = bad.sum()
+        p, s, t, g = p[~bad], s[~bad], t[~bad], g[~bad]
+        out[I_USED] = s.size
+        r = (s - t).astype(F32)
+        c0 = p[:, 1] * g[:, 2] - p[:, 2] * g[:, 1]
+        c1 = p[:, 2] * g[:, 0] - p[:, 0] * g[:, 2]
+        c2 = p[:, 0] * g[:, 1] - p[:, 1] * g[:, 0]
+        J = [g[:, 0], g[:, 1], g[:, 2], c0, c1, c2]
+        wgt = robust_weight(r, huber)
+        wJ = [wgt * x for x in J]
+        k = 0
+        for a in range(6):
+            for b in range(a, 6):
+                out[k] = fix(wJ[a] * J[b]).sum()
+                k += 1
+        for a in range(6):
+            out[21 + a] = fix(wJ[a] * r).sum()
+        out[I_E] = fix((wgt * r) * r).sum()
+    return out
+
+
 def linearize(depth, R, T, K, stride, vs, grid, d_min=0.3, d_max=5.0, r_max=0.4, g_max=4.0, huber=0.0, order=None):
     """The 33 integers of one linearisation.  depth uint16 [h, w]; R, T float64 (rounded to f32 once); K 9 values; grid = (val, known, lo);
     d_min / d_max / r_max / g_max / huber are the values after the defaults (r_max and g_max are rounded to f32 as the configuration holds them);
     order: a permutation of the visited pixels (the sums do not depend on it)."""
-    val, known, lo = grid
     depth = np.asarray(depth)
     assert depth.dtype == np.uint16 and depth.ndim == 2
     h, w = depth.shape
@@ -37,17 +83,13 @@ def linearize(depth, R, T, K, stride, vs, grid, d_min=0.3, d_max=5.0, r_max=0.4,
     fx, fy, cx, cy = (F32(K[i]) for i in (0, 4, 2, 5))
     vs = F32(vs)
     thr_min, thr_max = F32(float(d_min) * 1000.0), F32(float(d_max) * 1000.0)
-    r_max, g_max, huber = F32(r_max), F32(g_max), F32(huber)
-    gm2 = g_max * g_max
     jj, ii = np.meshgrid(np.arange(0, h, stride), np.arange(0, w, stride), indexing="ij")
     i, j = ii.ravel(), jj.ravel()
     if order is not None:
         i, j = i[order], j[order]
-    out = np.zeros(N_SUMS, np.int64)
     d = depth[j, i]
     df = d.astype(F32)
     gate = (d == 0) | (df > thr_max) | (df < thr_min)
-    out[I_GATE] = gate.sum()
     i, j, df = i[~gate], j[~gate], df[~gate]
     with np.errstate(invalid="ignore", over="ignore", divide="ignore"):
         dep = df / F32(1000.0)
@@ -55,34 +97,7 @@ def linearize(depth, R, T, K, stride, vs, grid, d_min=0.3, d_max=5.0, r_max=0.4,
         py = (j.astype(F32) - cy) * dep / fy
         pz = dep
         p = np.stack([((R[a, 0] * px + R[a, 1] * py) + R[a, 2] * pz) + T[a] for a in range(3)], 1).astype(F32)
-        s, kn, g = rv.sample(p, vs, val, known, lo)
-        out[I_UNKNOWN] = (~kn).sum()
-        p, s, g = p[kn], s[kn], (g[kn] / vs).astype(F32)
-        far = np.abs(s) > r_max
-        out[I_FAR] = far.sum()
-        p, s, g = p[~far], s[~far], g[~far]
-        gg = (g[:, 0] * g[:, 0] + g[:, 1] * g[:, 1]) + g[:, 2] * g[:, 2]
-        bad = (gg == 0) | (gg > gm2)
-        out[I_GRAD] = bad.sum()
-        p, s, g = p[~bad], s[~bad], g[~bad]
-        out[I_USED] = s.size
-        c0 = p[:, 1] * g[:, 2] - p[:, 2] * g[:, 1]
-        c1 = p[:, 2] * g[:, 0] - p[:, 0] * g[:, 2]
-        c2 = p[:, 0] * g[:, 1] - p[:, 1] * g[:, 0]
-        J = [g[:, 0], g[:, 1], g[:, 2], c0, c1, c2]
-        a_s = np.abs(s)
-        one = np.ones_like(s)
-        wgt = np.where((huber > 0) & (a_s > huber), huber / np.where(a_s > 0, a_s, one), one).astype(F32)
-        wJ = [wgt * x for x in J]
-        k = 0
-        for a in range(6):
-            for b in range(a, 6):
-                out[k] = fix(wJ[a] * J[b]).sum()
-                k += 1
-        for a in range(6):
-            out[21 + a] = fix(wJ[a] * s).sum()
-        out[I_E] = fix((wgt * s) * s).sum()
-    return out
+    return points(p, np.zeros(p.shape[0], F32), vs, grid, r_max, g_max, huber, n_gate=gate.sum())
 
 
 def system(sums, damping=0.0):
@@ -150,8 +165,9 @@ def retract(xi, R, T):
     return np.array(Rn, np.float64).reshape(3, 3), np.array(Tn, np.float64)
 
 
-def track(depth, R, T, K, vs, grid, levels=DEFAULT_LEVELS, min_step=1e-4, damping=0.0, min_used=6, **gates):
-    """(R, T, info) of tsl_tsdf_track_depth; info = dict(status, iterations, records), a record = dict(R, T, sums, xi, level)"""
+def iterate(lin, R, T, levels, min_step, damping, min_used):
+    """The iteration over the levels, shared by the alignment and the registration: lin(R, T, stride) gives the 33 integers at a float64 pose.
+    Returns (R, T, info); info = dict(status, iterations, records), a record = dict(R, T, sums, xi, level)"""
     R = np.array(R, np.float64).reshape(3, 3)
     T = np.array(T, np.float64).reshape(3)
     Rl, Tl = R.copy(), T.copy()
@@ -159,7 +175,7 @@ def track(depth, R, T, K, vs, grid, levels=DEFAULT_LEVELS, min_step=1e-4, dampin
     for lv, (stride, iters) in enumerate(levels):
         status = 1
         for _ in range(iters):
-            sums = linearize(depth, R, T, K, stride, vs, grid, **gates)
+            sums = lin(R, T, stride)
             lost = int(sums[I_USED]) < min_used
             xi, singular = ([0.0] * 6, False) if lost else solve(sums, damping)
             records.append(dict(R=R.copy(), T=T.copy(), sums=sums, xi=np.array(xi, np.float64), level=lv))
@@ -172,3 +188,8 @@ def track(depth, R, T, K, vs, grid, levels=DEFAULT_LEVELS, min_step=1e-4, dampin
                 status = 0
                 break
     return R, T, dict(status=status, iterations=len(records), records=records)
+
+
+def track(depth, R, T, K, vs, grid, levels=DEFAULT_LEVELS, min_step=1e-4, damping=0.0, min_used=6, **gates):
+    """(R, T, info) of tsl_tsdf_track_depth; info as iterate returns it"""
+    return iterate(lambda R, T, stride: linearize(depth, R, T, K, stride, vs, grid, **gates), R, T, levels, min_step, damping, min_used)
