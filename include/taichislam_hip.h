@@ -66,7 +66,7 @@ typedef struct {
 enum { TSL_K_VOXELIZE = 0, TSL_K_SORT = 1, TSL_K_RAYS = 2, TSL_K_INTEGRATE = 3, TSL_K_FINALIZE = 4,
        TSL_K_MESH = 5, TSL_K_SEGMENTS = 6, TSL_K_BIN = 7, TSL_K_ESDF = 8, TSL_K_FUSE = 9, TSL_K_REGISTER = 10,
        TSL_K_REGISTER_SCORE = 11, TSL_K_FRONTIER_MARK = 12, TSL_K_FRONTIER_LABEL = 13, TSL_K_FRONTIER_JOIN = 14, TSL_K_FRONTIER_SUM = 15,
-       TSL_K_FRONTIER_EMIT = 16, TSL_K_COUNT };
+       TSL_K_FRONTIER_EMIT = 16, TSL_K_VIEW_GAIN = 17, TSL_K_COUNT };
 
 const char* tsl_version(void);
 const char* tsl_last_error(void);
@@ -478,6 +478,44 @@ int  tsl_tsdf_frontier_extract(tsl_tsdf* m, const tsl_frontier_cfg* cfg, int32_t
 int  tsl_tsdf_frontier_read(tsl_tsdf* m, int16_t* idx, uint8_t* mask, int32_t* cluster, tsl_frontier_cluster* clusters, int64_t n_voxels, int64_t n_clusters);
 int  tsl_tsdf_frontier_dev(tsl_tsdf* m, const tsl_frontier_cfg* cfg, void** idx_dev, void** mask_dev, void** cluster_dev, void** clusters_dev,
                            int32_t* n_voxels, int32_t* n_clusters, void* user_stream);
+
+/* ---- view gain (tsl_view_gain.hip): for each of n candidate camera poses, how much unobserved space a sensor there would see before its rays hit
+ * something -- the figure a next-best-view planner ranks its candidates by.  One read-only launch for all poses; every output
+ * is an integer, so the result depends on no schedule and tests/view_gain_ref.py restates it bit for bit.  All f32, in the written order, no contraction.
+ *   Rays.  A view is a pinhole fan of h x w rays with intrinsics K; the pose R (row-major) / T is camera-to-map in the frame of tsl_tsdf_query_points
+ *     (the active submap's; submap 0 on a global map), given as doubles and rounded to f32 once on the host.  Ray (u, v): dc = ((u - cx) / fx,
+ *     (v - cy) / fy, 1), d = R dc (rows summed left to right, NOT normalised: the ray parameter is the optical-axis depth, as in tsl_tsdf_render_view).
+ *     Samples n = 0 .. S-1, S = (int)((t_max - t_min) / dt) + 1, t_n = t_min + (float)n * dt, p_n = T + t_n * d, u_n = p_n / voxel.
+ *   Class of a sample.  Its voxel is rnd(clamp(u_n)) per axis: clamp(x) = max(min(x, 2^24), -2^24) keeps the conversion inside an int (the clamp of
+ *     the renderer's cell index), rnd is the project's round-half-away-from-zero, (int)(x + copysign(0.49999997f, x)).  The sample is OUTSIDE when a
+ *     coordinate of p_n is not finite or the voxel is not in the volume; otherwise it has the class tsl_tsdf_frontier_extract gives that voxel:
+ *     UNKNOWN (brick absent or observed count <= 0), OCCUPIED (observed and the f16 TSDF widened to f32 < thres), FREE.  thres = free_thres, 0 = the
+ *     map's surface threshold (float)(voxel * 1.8).
+ *   Walk.  An OUTSIDE sample counts nothing and changes no state (the space outside the volume is not unknown).  The first OCCUPIED sample ends the ray
+ *     with status 0 (hit) and is not counted.  A FREE sample adds 1 to the ray's free count, w_n to its free weight, and sets the unknown run to 0.  An
+ *     UNKNOWN sample adds 1 to the unknown count, w_n to the unknown weight and 1 to the run; with unknown_run > 0 the ray ends with status 2 (cut) once
+ *     the run reaches unknown_run, the sample that reaches it counted (the pessimistic model: unknown space may hide a wall).  A ray that reaches S
+ *     ends with status 1 (range).  A ray "looks through a frontier" when some UNKNOWN sample's previous non-OUTSIDE sample was FREE.
+ *   Weight.  w_n = rnd((t_n * t_n) * 1024.0f).  The volume element of a ray at optical depth t is t^2 dt / (fx fy), so sum(w) / 1024 * dt / (fx * fy)
+ *     is the volume in cubic metres the fan sees of that class -- the left Riemann sum is the definition.  t_max <= 1024 keeps w below 2^31.
+ *   tsl_view_gain (64 bytes, one per pose): the sums over the pose's rays of the unknown / free counts and weights, the rays per status, and
+ *     n_frontier, the rays that look through a frontier.  Optional per-ray outputs (both or neither): ray_unknown int32 [n][h][w], the ray's unknown
+ *     count, and ray_status u8 [n][h][w], the status | 0x10 for a ray that looked through a frontier.
+ *   tsl_gain_cfg: K, t_min, t_max, dt with the defaults of tsl_view_cfg (all-zero K = the map's depth intrinsics, 0 = the map's min / max_ray_length,
+ *     dt 0 = 0.75 voxel); flags bit 0 evaluates every sample instead of jumping over the space outside the volume and over unallocated bricks: the same
+ *     result bit for bit (the A/B switch).
+ * tsl_tsdf_view_gain issues the queued frames, runs on the handle's stream behind them, waits and copies back.  tsl_tsdf_view_gain_dev is
+ * ASYNCHRONOUS and ordered with `user_stream` like tsl_tsdf_render_view_dev; out_dev holds n records (as int32 [n][16]).  The call reads one submap slot
+ * and writes nothing to the map or the ESDF.  With profiling on, tsl_tsdf_prof_query(m, TSL_K_VIEW_GAIN) returns the time of the kernel alone.
+ * TSL_ERR_ARG (the text names the entry point): a null handle, pose array, cfg or out; n outside 0 .. 65536 (n = 0 does nothing: TSL_OK); a pose,
+ * intrinsic, range or threshold that is not finite; h or w outside 1 .. 4096; t_max <= t_min; dt <= 0; t_max > 1024; more than 2^24 samples per ray;
+ * unknown_run < 0; exactly one of the two per-ray buffers.  A refused call leaves the handle usable. */
+typedef struct { double K[9]; int32_t h, w; float t_min, t_max, dt, free_thres; int32_t unknown_run, flags; } tsl_gain_cfg;
+typedef struct { int64_t n_unknown, n_free, vol_unknown, vol_free; int32_t n_hit, n_range, n_cut, n_frontier; int32_t reserved_[4]; } tsl_view_gain;
+int  tsl_tsdf_view_gain(tsl_tsdf* m, const double* R /* n x 9 */, const double* T /* n x 3 */, int32_t n, const tsl_gain_cfg* cfg, tsl_view_gain* out,
+                        int32_t* ray_unknown, uint8_t* ray_status);
+int  tsl_tsdf_view_gain_dev(tsl_tsdf* m, const double* R, const double* T, int32_t n, const tsl_gain_cfg* cfg, void* out_dev, void* ray_unknown_dev,
+                            void* ray_status_dev, void* user_stream);
 
 /* backend knobs for A/B-ing kernel variants: name in
      "variant"  0|1: one global int64 atomic pair per ray step, 2 (default): brick-binned LDS accumulation

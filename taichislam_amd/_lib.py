@@ -8,10 +8,11 @@ from . import build as _build
 TSL_OK = 0
 K_VOXELIZE, K_SORT, K_RAYS, K_INTEGRATE, K_FINALIZE, K_MESH, K_SEGMENTS, K_BIN, K_ESDF, K_FUSE, K_REGISTER, K_REGISTER_SCORE = range(12)
 K_FRONTIER_MARK, K_FRONTIER_LABEL, K_FRONTIER_JOIN, K_FRONTIER_SUM, K_FRONTIER_EMIT = range(12, 17)
+K_VIEW_GAIN = 17
 KERNEL_NAMES = {K_VOXELIZE: "voxelize", K_SORT: "sort", K_RAYS: "build_rays", K_INTEGRATE: "integrate",
                 K_FINALIZE: "finalize", K_MESH: "marching_cubes", K_SEGMENTS: "segments", K_BIN: "bin", K_ESDF: "esdf", K_FUSE: "fuse", K_REGISTER: "register",
                 K_REGISTER_SCORE: "register_score", K_FRONTIER_MARK: "frontier_mark", K_FRONTIER_LABEL: "frontier_label", K_FRONTIER_JOIN: "frontier_join",
-                K_FRONTIER_SUM: "frontier_sum", K_FRONTIER_EMIT: "frontier_emit"}
+                K_FRONTIER_SUM: "frontier_sum", K_FRONTIER_EMIT: "frontier_emit", K_VIEW_GAIN: "view_gain"}
 
 
 class TsdfCfg(C.Structure):
@@ -128,6 +129,19 @@ class FrontierCluster(C.Structure):
                 ("reserved_", C.c_int32 * 2)]
 
 
+class GainCfg(C.Structure):
+    """tsl_gain_cfg (tsl_tsdf_view_gain): a zero K / t_min / t_max / dt / free_thres means the map's default, unknown_run 0 = no cut, flags bit 0 = every
+    sample is evaluated"""
+    _fields_ = [("K", C.c_double * 9), ("h", C.c_int32), ("w", C.c_int32), ("t_min", C.c_float), ("t_max", C.c_float), ("dt", C.c_float),
+                ("free_thres", C.c_float), ("unknown_run", C.c_int32), ("flags", C.c_int32)]
+
+
+class ViewGain(C.Structure):
+    """tsl_view_gain: 64 bytes per pose, the layout of VIEW_GAIN_DTYPE"""
+    _fields_ = [("n_unknown", C.c_int64), ("n_free", C.c_int64), ("vol_unknown", C.c_int64), ("vol_free", C.c_int64), ("n_hit", C.c_int32),
+                ("n_range", C.c_int32), ("n_cut", C.c_int32), ("n_frontier", C.c_int32), ("reserved_", C.c_int32 * 4)]
+
+
 class TslError(RuntimeError):
     pass
 
@@ -226,6 +240,8 @@ SIGNATURES = {
     "tsl_tsdf_frontier_extract": (C.c_int, [vp, C.POINTER(FrontierCfg), pi32, pi32]),
     "tsl_tsdf_frontier_read": (C.c_int, [vp, vp, vp, vp, vp, i64, i64]),
     "tsl_tsdf_frontier_dev": (C.c_int, [vp, C.POINTER(FrontierCfg), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), pi32, pi32, vp]),
+    "tsl_tsdf_view_gain": (C.c_int, [vp, dp, dp, i32, C.POINTER(GainCfg), vp, vp, vp]),
+    "tsl_tsdf_view_gain_dev": (C.c_int, [vp, dp, dp, i32, C.POINTER(GainCfg), vp, vp, vp, vp]),
     "tsl_tsdf_set_option": (C.c_int, [vp, C.c_char_p, C.c_int]),
     "tsl_tsdf_get_option": (C.c_int, [vp, C.c_char_p, C.POINTER(C.c_int)]),
     "tsl_tsdf_prof_enable": (C.c_int, [vp, C.c_int]),

@@ -221,6 +221,8 @@ int esdf_finish(tsl_tsdf* m);            // tsl_esdf.hip: wait for the ESDF upda
 void esdf_release(tsl_tsdf* m);
 struct FrontierState;                    // tsl_frontier.hip: scratch and result of the frontier extraction
 void frontier_release(tsl_tsdf* m);
+struct GainState;                        // tsl_view_gain.hip: the pinned staging of a call's pose table
+void gain_release(tsl_tsdf* m);
 }  // namespace tsl
 
 #define TSL_ESDF_SLOTS 4
@@ -287,6 +289,7 @@ struct tsl_tsdf {
     void *seqb_keys[TSL_NBATCH][2], *seqb_vals[TSL_NBATCH][2], *seqb_temp[TSL_NBATCH], *seqb_long[TSL_NBATCH], *seqb_lmask[TSL_NBATCH], *seqb_perm[TSL_NBATCH]; size_t seqb_temp_bytes; long long seq_tuple_cap;      // per batch slot: the rays' struct-for keys of all its frames, sorted in one call
     unsigned long long *seq_keys[2], *seq_vals[2], *seq_ctr; void* seq_temp; size_t seq_temp_bytes; long long seq_cap;
     tsl::FrontierState* frontier;        // tsl_frontier.hip (allocated by the first extraction)
+    tsl::GainState* gain;                // tsl_view_gain.hip (allocated by the first call)
     int variant, split, phases, wg, spt, ncu, chunks, unit_max, unit_half, unit_floor, bgrid, ugrid, pgrid, split_launch, adaptive, ramp, ramp_batches, ramp_size; bool clean; uint64_t batch_gen;
     int64_t bytes;
     void* seqv_sum[TSL_NBATCH]; int* seqv_log;      // TSL_SEQ_VERIFY (developer aid, tsl_sequential.hip): per-item checksums, mismatch log

@@ -201,6 +201,116 @@ def frontier_cluster_geometry(clusters, voxel_scale):
     return centroid.reshape(-1, 3), normal.reshape(-1, 3)
 
 
+# tsl_view_gain (include/taichislam_hip.h): 64 bytes per pose at fixed offsets
+VIEW_GAIN_DTYPE = np.dtype({"names": ["n_unknown", "n_free", "vol_unknown", "vol_free", "n_hit", "n_range", "n_cut", "n_frontier"],
+                            "formats": [np.int64, np.int64, np.int64, np.int64, np.int32, np.int32, np.int32, np.int32],
+                            "offsets": [0, 8, 16, 24, 32, 36, 40, 44], "itemsize": 64})
+
+
+def gain_intrinsics(K, stride):
+    """Row-major K [9] of the fan that takes every stride-th pixel of the image K describes: fx / stride, (cx + 0.5) / stride - 0.5, the same for y, in float64"""
+    k = np.asarray(K, dtype=np.float64).reshape(-1).copy()
+    if k.size != 9 or not np.isfinite(k).all() or not k.any():
+        raise ValueError("score_views: K must hold 9 finite values, not all zero")
+    s = float(stride)
+    k[0], k[4] = k[0] / s, k[4] / s
+    k[2], k[5] = (k[2] + 0.5) / s - 0.5, (k[5] + 0.5) / s - 0.5
+    return k
+
+
+def gain_config(K=None, shape=(60, 80), stride=1, t_min=None, t_max=None, step=None, free_thres=None, unknown_run=0, skip=True):
+    """The tsl_gain_cfg of DenseTSDF.score_views; None = the map's default (passed as 0).  The fan is every stride-th pixel of the `shape` image:
+    ceil(h / stride) x ceil(w / stride) rays (a stride > 1 needs K).  Raises ValueError for values no fan can have."""
+    cfg = _lib.GainCfg()
+    stride = int(stride)
+    if stride < 1:
+        raise ValueError("score_views: stride must be at least 1")
+    if K is not None:
+        cfg.K[:] = gain_intrinsics(K, stride).tolist()
+    elif stride > 1:
+        raise ValueError("score_views: a stride needs the intrinsics it scales")
+    h, w = (int(x) for x in shape)
+    if h <= 0 or w <= 0:
+        raise ValueError("score_views: shape must be (h, w) with h, w > 0")
+    cfg.h, cfg.w = -(-h // stride), -(-w // stride)
+    if cfg.h > 4096 or cfg.w > 4096:
+        raise ValueError("score_views: at most 4096 rays per side")
+    for name, v in (("t_min", t_min), ("t_max", t_max), ("dt", step), ("free_thres", free_thres)):
+        if v is None:
+            continue
+        v = float(v)
+        if not math.isfinite(v) or (v <= 0.0 and name != "t_min") or v == 0.0:
+            raise ValueError(f"score_views: {name if name != 'dt' else 'step'} must be finite" + (" and positive" if name != "t_min" else " and not 0 (0 stands for the default)"))
+        setattr(cfg, name, v)
+    if int(unknown_run) < 0:
+        raise ValueError("score_views: unknown_run must not be negative")
+    cfg.unknown_run = int(unknown_run)
+    cfg.flags = 0 if skip else 1
+    return cfg
+
+
+def gain_poses(R, T):
+    """(R float64 [n, 9], T float64 [n, 3]) of the poses of DenseTSDF.score_views: R [n, 3, 3] or [3, 3], T [n, 3] or [3]"""
+    R, T = np.asarray(R, dtype=np.float64), np.asarray(T, dtype=np.float64)
+    if R.ndim == 2 and R.shape == (3, 3) and T.shape == (3,):
+        R, T = R[None], T[None]
+    if R.ndim != 3 or R.shape[1:] != (3, 3) or T.ndim != 2 or T.shape != (R.shape[0], 3):
+        raise ValueError("score_views: R must be [n, 3, 3] or [3, 3] and T [n, 3] or [3], the same n")
+    if R.shape[0] > 65536:
+        raise ValueError("score_views: at most 65536 poses")
+    if not (np.isfinite(R).all() and np.isfinite(T).all()):
+        raise ValueError("score_views: a pose is not finite")
+    return np.ascontiguousarray(R.reshape(-1, 9)), np.ascontiguousarray(T)
+
+
+def gain_volume(vol, step, fx, fy):
+    """Cubic metres of a weight sum of tsl_view_gain: sum(w) / 1024 * dt / (fx * fy), float64 (step, fx, fy: the f32 values the library used)"""
+    return np.asarray(vol, dtype=np.float64) / 1024.0 * float(np.float32(step)) / (float(np.float32(fx)) * float(np.float32(fy)))
+
+
+def frontier_view_candidates(frontiers, standoff, yaws=1, up=(0.0, 0.0, 1.0)):
+    """Candidate camera poses from the `centroid` / `normal` arrays of DenseTSDF.extract_frontiers: per cluster a camera `standoff` metres back from the
+    centroid, against the cluster's direction into the unknown, looking along it (optical convention: x right, y down, z forward; y as close to -up as the
+    direction allows).  yaws > 1 places that many headings per cluster, the direction turned about `up` by 2 pi j / yaws, each camera still `standoff` metres
+    from the centroid and looking at it.  Clusters whose normal is 0 are skipped.  Returns (R float64 [m, 3, 3], T float64 [m, 3]), cluster-major,
+    camera-to-map in the frame of extract_frontiers: what DenseTSDF.score_views takes."""
+    c = np.asarray(frontiers["centroid"], dtype=np.float64).reshape(-1, 3)
+    nrm = np.asarray(frontiers["normal"], dtype=np.float64).reshape(-1, 3)
+    yaws = int(yaws)
+    if yaws < 1:
+        raise ValueError("frontier_view_candidates: yaws must be at least 1")
+    standoff = float(standoff)
+    if not math.isfinite(standoff):
+        raise ValueError("frontier_view_candidates: standoff is not finite")
+    upv = np.asarray(up, dtype=np.float64).reshape(3)
+    ul = np.linalg.norm(upv)
+    if not ul > 0.0:
+        raise ValueError("frontier_view_candidates: up must not be 0")
+    upv = upv / ul
+    Rs, Ts = [], []
+    for ci, ni in zip(c, nrm):
+        ln = np.linalg.norm(ni)
+        if not ln > 0.0:
+            continue
+        z0 = ni / ln
+        for j in range(yaws):
+            if j == 0:
+                z = z0
+            else:                                                      # Rodrigues: z0 turned about up by 2 pi j / yaws
+                a = 2.0 * math.pi * j / yaws
+                z = z0 * math.cos(a) + np.cross(upv, z0) * math.sin(a) + upv * float(upv @ z0) * (1.0 - math.cos(a))
+            x = np.cross(z, upv)
+            if np.linalg.norm(x) < 1e-9:                               # looking along up: any horizontal axis serves
+                x = np.cross(z, np.array([1.0, 0.0, 0.0]) if abs(upv[0]) < 0.9 else np.array([0.0, 1.0, 0.0]))
+            x = x / np.linalg.norm(x)
+            y = np.cross(z, x)
+            Rs.append(np.stack([x, y, z], 1))
+            Ts.append(ci - standoff * z)
+    if not Rs:
+        return np.zeros((0, 3, 3)), np.zeros((0, 3))
+    return np.stack(Rs), np.stack(Ts)
+
+
 def _depth_image(depth):
     """(pointer, (h, w), keep-alive, is_device) of a uint16 millimetre image: a numpy array or a torch CUDA tensor, the forms recast_depth_to_map accepts"""
     if _is_device_tensor(depth):
@@ -749,6 +859,54 @@ class DenseTSDF(BaseMap):
         status = np.empty((h, w), np.uint8)
         _lib.check(self.L.tsl_tsdf_render_view(self.h, r, t, C.byref(cfg), _vp(depth), _vp(normal), _vp(rgb), _vp(status)))
         return depth, normal, rgb, status
+
+    # ---- view gain (tsl_view_gain.hip) --------------------------------------------------------------
+    def score_views(self, R, T, K=None, shape=(60, 80), stride=1, t_min=None, t_max=None, step=None, free_thres=None, unknown_run=0, rays=False,
+                    device=False, skip=True):
+        """Scores candidate camera poses by the unobserved space a sensor there would see: R [n, 3, 3] (or [3, 3]), T [n, 3] (or [3]) camera-to-map in the
+        frame of is_pos_occupy / render_view.  Per pose a pinhole fan -- every stride-th pixel of the `shape` image with intrinsics K (default: the map's
+        depth intrinsics) -- is walked every `step` metres of depth (default 0.75 voxel) from t_min to t_max (default: the map's min / max_ray_length);
+        a sample has the class extract_frontiers gives its nearest voxel (free_thres as there), samples outside the volume count nothing, the first
+        occupied sample ends the ray; with unknown_run > 0 so do that many unknown samples in a row (unknown space may hide a wall).  Returns a dict of
+        arrays per pose: n_unknown, n_free (samples), vol_unknown, vol_free (the same weighted by rnd(t^2 * 1024)), n_hit, n_range, n_cut (rays per
+        status), n_frontier (rays on which an unknown sample follows a free one), and unknown_volume / free_volume, float64 cubic metres
+        (vol / 1024 * step / (fx * fy)); with rays=True also ray_unknown int32 [n, h, w] and ray_status u8 [n, h, w] (0 hit, 1 range, 2 cut, | 0x10
+        through a frontier).  Every integer is exact and independent of the schedule.  skip=False evaluates every sample instead of jumping over the
+        outside and over unallocated bricks: the same result, slower (the A/B switch).  device=True returns torch tensors on the map's device,
+        asynchronously, ordered with torch.cuda.current_stream: `records` int32 [n, 16] (the tsl_view_gain records) and the per-ray arrays."""
+        Kuse = K
+        if K is None and self.K_cam_dep is not None:
+            Kuse = self.K_cam_dep                                    # the values the library holds: passed so that the stride can scale them
+        if Kuse is None:
+            raise ValueError("score_views: the map has no depth intrinsics; pass K")
+        cfg = gain_config(Kuse, shape, stride, t_min, t_max, step, free_thres, unknown_run, skip)
+        Rn, Tn = gain_poses(R, T)
+        n, h, w = Rn.shape[0], cfg.h, cfg.w
+        r, t = Rn.ctypes.data_as(_lib.dp), Tn.ctypes.data_as(_lib.dp)
+        if device:
+            torch = _torch()
+            dev = torch.device(f"cuda:{self.device}")
+            rec = torch.zeros((n, 16), dtype=torch.int32, device=dev)
+            ru = torch.zeros((n, h, w), dtype=torch.int32, device=dev) if rays else None
+            rs = torch.zeros((n, h, w), dtype=torch.uint8, device=dev) if rays else None
+            if n:
+                _lib.check(self.L.tsl_tsdf_view_gain_dev(self.h, r, t, n, C.byref(cfg), rec.data_ptr(), None if ru is None else ru.data_ptr(),
+                                                         None if rs is None else rs.data_ptr(), torch.cuda.current_stream(dev).cuda_stream))
+            out = {"records": rec}
+            if rays:
+                out["ray_unknown"], out["ray_status"] = ru, rs
+            return out
+        rec = np.zeros(n, VIEW_GAIN_DTYPE)
+        ru = np.zeros((n, h, w), np.int32) if rays else None
+        rs = np.zeros((n, h, w), np.uint8) if rays else None
+        _lib.check(self.L.tsl_tsdf_view_gain(self.h, r, t, n, C.byref(cfg), _vp(rec), _vp(ru), _vp(rs)))
+        out = {k: rec[k].copy() for k in VIEW_GAIN_DTYPE.names}
+        dt = np.float32(cfg.dt) if cfg.dt != 0.0 else np.float32(0.75) * np.float32(self.voxel_scale)
+        out["unknown_volume"] = gain_volume(out["vol_unknown"], dt, cfg.K[0], cfg.K[4])
+        out["free_volume"] = gain_volume(out["vol_free"], dt, cfg.K[0], cfg.K[4])
+        if rays:
+            out["ray_unknown"], out["ray_status"] = ru, rs
+        return out
 
     # ---- exploration frontiers (tsl_frontier.hip, DESIGN.md section 4.11) ---------------------------------------------------
     def extract_frontiers(self, free_thres=None, z_range=None, min_unknown=1, connectivity=26, min_cluster=1, clear_of_occupied=False, device=False):
