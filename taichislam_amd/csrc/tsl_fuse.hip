@@ -65,10 +65,12 @@ __global__ void __launch_bounds__(256) k_fuse_splat(MapDev S, MapDev G, PoseTab 
 // The same splat with the sums gathered in LDS first (round 6; untextured maps -- the common case and the multi-GPU merge).  k_fuse_splat issues 21 global atomics
 // per source voxel (7 corners x {num, den, count}): 57 M int64 / int32 atomics for one 2.7 M-voxel submap, 0.86 ms, and the write counter saw 8x the bytes the
 // fusion has to move.  Neighbouring source voxels splat onto the SAME global voxels -- a global voxel takes ~7 contributions -- so a workgroup takes an 8^3
-// block of a source brick, whose 7 corner splats land in a window of at most 15^3 global voxels whatever the pose (a cube of 7 voxel spans has a diagonal of
-// 12.2: 13 floors, + 1 for the far corner, + 1 of slack for the rounding of the pose product), sums them there with LDS atomics and flushes every window voxel
-// that got something with ONE set of global atomics: 3.5x fewer.  Exact integer sums: the grouping cannot change a bit.  (A corner outside the window -- not
-// seen, the window is sized for the worst pose -- goes straight to memory like before.)
+// block of a source brick and a window of 15^3 global voxels placed one below the least floor of the block's eight corner voxels, sums the block's corner
+// splats there with LDS atomics and flushes every window voxel that got something with ONE set of global atomics: 3.5x fewer.  Exact integer sums: the
+// grouping cannot change a bit.  The window holds every corner for yaw-like poses.  It is NOT sized for the worst rotation: a cube of 7 voxel spans has a
+// body diagonal of 7 * sqrt(3) = 12.12, which can straddle 14 floors; + 1 for the far corner and + 1 for org = min - 1 is window index 15 = FW.  Near a
+// body-diagonal rotation a few corners per thousand leave the window (48 of 229 376 for the case pinned in tests/test_fuse_window_cpu.py) and go straight
+// to memory like before: a miss costs time and is exact.  (FW = 16 would hold every rigid pose, at 80 KiB of LDS per workgroup against 67.5 KiB: unmeasured.)
 #define FW 15
 #define FW3 (FW * FW * FW)
 __global__ void __launch_bounds__(256) k_fuse_splat_lds(MapDev S, MapDev G, PoseTab poses, float vs, int nused, unsigned long long* acc, int* cnt, int npose)
@@ -127,7 +129,7 @@ __global__ void __launch_bounds__(256) k_fuse_splat_lds(MapDev S, MapDev G, Pose
                     __hip_atomic_fetch_add(&s_den[e], qd, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);                     // :274
                     __hip_atomic_fetch_add(&s_cnt[e], (1 << 16) + occ, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);        // :279-280
                 } else {
-                    atomicAdd(G.pool_top + 2, 1);                      // (counted: option "fuse_window_misses" -- the tests require 0)
+                    atomicAdd(G.pool_top + 2, 1);                      // (counted: option "fuse_window_misses" -- 0 for yaw-like poses; tests/test_fuse_poses_gpu.py requires the count tests/fuse_window_ref.py predicts)
                     int gl; const int gb = brick_of(G, ci, cj, ck, &gl);
                     const int gp = pool_claim<false>(G, 0, gb);
                     if (gp < 0) continue;
