@@ -207,10 +207,23 @@ int  tsl_mesh_read(tsl_tsdf* m, float* verts, float* normals, float* colors, int
  * for untextured maps), + num_facelets of the last generate: taichislam_node.py:342 without the host copy */
 int  tsl_mesh_buffers_dev(tsl_tsdf* m, void** verts_dev, void** normals_dev, void** colors_dev, int32_t* n_tri);
 
+/* ---- coordinates that are not finite ----------------------------------------------------------------------------------------------
+ * A coordinate that is not finite (NaN, +-inf), or whose cell index rnd(x / voxel) does not fit an int, lies OUTSIDE every map.  The entry points that
+ * take coordinates from a caller without a range gate say so with an explicit test, never with a float-to-int conversion (which is undefined in C
+ * and turns NaN into cell 0 on gfx950):
+ *   - Octomap inserts (points, depth pixels) and tsl_octo_fuse_submaps: the point / leaf counts in p_oob and touches no leaf;
+ *   - tsl_tsdf_query_points[_dev]: the voxel reads as outside -- TSDF 0, unobserved: modes 0 and 1 give 1, mode 2 gives 1 for param > 0;
+ *   - tsl_tsdf_query_raycast[_dev]: a step whose position is not finite reads as outside, so the ray "hits" there; a NaN component of end_xyz is
+ *     written as the quiet NaN 0x7fc00000 (which NaN an invalid operation produces differs between processors);
+ *   - tsl_tsdf_integrate_points[_dev]: the point fails the gate `len < max_ray_length` and counts in no statistic but p_used.
+ * The CPU oracle states the same (oracle/tsl_oracle.h); tests/test_octomap_limits_gpu.py and tests/test_query_edges_gpu.py hold both to it.
+ * (Poses and intrinsics that are not finite are refused by the newer entry points; on the ones above they are the caller's business.) */
+
 /* ---- batched map queries  (mapping_common.py:165-204, dense_tsdf.py:148-155; consumers: topo_graph.py:444-507) ---------- */
-/* mode 0: is_pos_occupy, 1: is_pos_unobserved, 2: is_near_pos_occupy(param voxels); xyz f32 [n][3] in the active submap's frame */
+/* mode 0: is_pos_occupy, 1: is_pos_unobserved, 2: is_near_pos_occupy(param voxels, 0 .. 16); xyz f32 [n][3] in the active submap's frame */
 int  tsl_tsdf_query_points(tsl_tsdf* m, int mode, int param, const float* xyz, int64_t n, uint8_t* out);
-/* raycast(pos, dir, max_dist) per query: hit flag, last evaluated position, length travelled */
+/* raycast(pos, dir, max_dist) per query: hit flag, last evaluated position, length travelled; (int)(max_dist / voxel) steps of one voxel.
+ * TSL_ERR_ARG, before anything is launched or written, for a max_dist that is negative or not finite (its step count would never end). */
 int  tsl_tsdf_query_raycast(tsl_tsdf* m, const float* pos, const float* dir, float max_dist, int64_t n, uint8_t* hit, float* end_xyz, float* len);
 /* the same with DEVICE buffers, asynchronous: launched on the handle's stream (behind every queued frame) after the work already queued
  * on `user_stream` (a hipStream_t, e.g. torch's current stream; NULL = the legacy default stream), and `user_stream` waits for the
@@ -646,8 +659,11 @@ int  tsl_octo_integrate_depth(tsl_octo* m, const double R[9], const double T[3],
  * tsl_octo_sync (or any call that returns map contents). */
 int  tsl_octo_integrate_depth_dev(tsl_octo* m, const double R[9], const double T[3], const void* depth_dev, int h, int w,
                                   const void* tex_dev, int th, int tw);
+/* recast_pcl_to_map has no range gate: a point outside the tree, or with a coordinate that is not finite (see "coordinates that are not finite"), counts in p_oob */
 int  tsl_octo_integrate_points(tsl_octo* m, const double R[9], const double T[3], const float* xyz, const uint8_t* rgb, int64_t n);   /* :126-128,134-145 */
 int  tsl_octo_integrate_points_dev(tsl_octo* m, const double R[9], const double T[3], const void* xyz_dev, const void* rgb_dev, int64_t n);   /* device buffers: f32 [n][3], u8 [n][3] or NULL */
+/* the statistics of the last insert.  TSL_ERR_CAPACITY (once: the flag is cleared by the read, and by tsl_octo_reset) when an insert since the last read found
+ * the brick pool (max_bricks) full: the points of the bricks that did not get in count in p_oob, the bricks that did hold exact counts */
 int  tsl_octo_last_frame_stats(tsl_octo* m, tsl_frame_stats* out);
 /* every touched leaf of the active submap: index, hit count and (textured maps; else zeros) colour f32[n][3]; rgb may be NULL */
 int  tsl_octo_export_leaves(tsl_octo* m, int32_t* idx, float* cnt, float* rgb, int64_t cap, int64_t* n);

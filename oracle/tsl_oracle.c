@@ -13,6 +13,8 @@
  * Build with -ffp-contract=off (no FMA contraction) -- the HIP side does the same.
  */
 #include "tsl_oracle.h"
+#include <float.h>
+#include <limits.h>
 #include <math.h>
 #include <stdlib.h>
 #include <string.h>
@@ -81,7 +83,9 @@ static inline float rnd_f(float x)
     if (d >= 0.5f) r += copysignf(1.0f, x);
     return r;
 }
-static inline int rnd_i(float x) { return (int)rnd_f(x); }
+/* A coordinate that is not finite, or whose cell index does not fit an int, lies outside every map (tsl_oracle.h, "coordinates that are not finite"):
+ * such a quotient is never cast (undefined in C), it becomes INT_MIN, which in_volume() rejects on every axis. */
+static inline int rnd_i(float x) { float r = rnd_f(x); return fabsf(r) < 2147483648.0f ? (int)r : INT_MIN; }
 static inline int sgn_f(float v) { return (0.0f < v) - (v < 0.0f); }   /* mapping_common.py:5-7 */
 
 /* per-frame accumulators are 2^-24 fixed point (BATCHED mode) */
@@ -1134,6 +1138,7 @@ void ora_tsdf_query_points(const ora_tsdf* m, int mode, int param, const float* 
         int r = 0;
         if (mode == 0) r = q_occupied(m, s, i, j, k);
         else if (mode == 1) { int o; (void)rd_tsdf(m, s, i, j, k, &o); r = o == 0; }
+        else if (i == INT_MIN || j == INT_MIN || k == INT_MIN) r = param > 0;             /* outside every map, and so is each of its (2 * param)^3 neighbours: no `INT_MIN + a` is formed */
         else for (int a = -param; a < param; ++a) for (int b = -param; b < param; ++b) for (int c = -param; c < param; ++c) r |= q_occupied(m, s, i + a, j + b, k + c);
         out[q] = (uint8_t)r;
     }
@@ -1142,15 +1147,17 @@ void ora_tsdf_query_raycast(const ora_tsdf* m, const float* pos, const float* di
 {
     int s = map_slot(m, m->active);
     float vs_len = (float)m->cfg.voxel_scale;
+    if (!(max_dist >= 0.0f && max_dist <= FLT_MAX)) return;                               /* refused (TSL_ERR_ARG in the product): the step count of such a length is never formed */
     for (int64_t q = 0; q < n; ++q) {
-        int steps = (int)(max_dist / m->vs);
+        const float sf = max_dist / m->vs;
+        int steps = sf < 2147483648.0f ? (int)sf : INT_MAX;
         float x[3] = {0, 0, 0}, l = 0.0f; int succ = 0;
         for (int jj = 0; jj < steps; ++jj) {
             l = (float)jj * vs_len;
             for (int a = 0; a < 3; ++a) x[a] = dir[q * 3 + a] * l + pos[q * 3 + a];
             if (q_occupied(m, s, rnd_i(x[0] / m->vs), rnd_i(x[1] / m->vs), rnd_i(x[2] / m->vs))) { succ = 1; break; }
         }
-        hit[q] = (uint8_t)succ; for (int a = 0; a < 3; ++a) end_xyz[q * 3 + a] = x[a]; len[q] = l;
+        hit[q] = (uint8_t)succ; for (int a = 0; a < 3; ++a) end_xyz[q * 3 + a] = x[a] != x[a] ? bits_f32(0x7fc00000u) : x[a]; len[q] = l;      /* a NaN leaves as the quiet NaN 0x7fc00000 (0 * inf is 0xffc00000 on x86) */
     }
 }
 

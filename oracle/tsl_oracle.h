@@ -109,6 +109,12 @@ int ora_tsdf_fuse_finalize_dense(ora_tsdf* global, const int64_t* acc, const int
 int64_t ora_mesh_generate(const ora_tsdf* m, int step, float surface_thres, int64_t max_tri,
                           float* verts, float* normals, float* colors);
 
+/* Coordinates that are not finite.  A coordinate that is not finite, or whose cell index does not fit an int, lies outside every map: rnd_i() in
+ * tsl_oracle.c and tsl_oracle_octo.c returns INT_MIN for such a quotient and never casts it (the cast is undefined in C; x86 happens to give INT_MIN).
+ * So: an Octomap point or fused leaf there counts in p_oob and touches no leaf; a queried voxel reads as outside (modes 0 and 1 give 1, mode 2
+ * gives param > 0 without forming INT_MIN + a); a ray step there reads as outside and the ray "hits"; a NaN component of end_xyz is written as
+ * 0x7fc00000; a TSDF cloud point there fails `len < max_ray_length`.  ora_tsdf_query_raycast returns without writing for a max_dist that is
+ * negative or not finite (the product returns TSL_ERR_ARG), and clamps the step count of a huge one to INT_MAX. */
 void ora_tsdf_query_points(const ora_tsdf* m, int mode, int param, const float* xyz, int64_t n, uint8_t* out);
 void ora_tsdf_query_raycast(const ora_tsdf* m, const float* pos, const float* dir, float max_dist, int64_t n, uint8_t* hit, float* end_xyz, float* len);
 

@@ -3,6 +3,7 @@
  * Restates taichi_slam/mapping/taichi_octomap.py; parity pinned to the reference's source run on tools/ti_seq (tests/golden/ref_octomap.npz; see tsl_oracle.h).
  */
 #include "tsl_oracle.h"
+#include <limits.h>
 #include <math.h>
 #include <stdlib.h>
 #include <string.h>
@@ -14,7 +15,8 @@ static inline float rnd_f(float x)
     if (d >= 0.5f) r += copysignf(1.0f, x);
     return r;
 }
-static inline int rnd_i(float x) { return (int)rnd_f(x); }
+/* a quotient that is not finite or does not fit an int is never cast: it becomes INT_MIN, outside every tree (tsl_oracle.h, "coordinates that are not finite") */
+static inline int rnd_i(float x) { float r = rnd_f(x); return fabsf(r) < 2147483648.0f ? (int)r : INT_MIN; }
 
 typedef struct { int32_t c[3]; float cnt; float col[3]; int used; int32_t wkey[4]; } leaf_t;      /* wkey: source of col after a fusion (submap, i, j, k) */
 typedef struct { leaf_t* a; int nslots, n; } leafmap;

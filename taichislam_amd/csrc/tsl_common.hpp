@@ -63,6 +63,10 @@ __device__ __forceinline__ float rnd_f(float x)
 // identity against rnd_f for every float.
 __device__ __forceinline__ int rnd_i(float x) { return (int)(x + copysignf(0.49999997f, x)); }
 __device__ __forceinline__ int rnd_i_ref(float x) { return (int)rnd_f(x); }
+// A coordinate that is not finite, or whose cell index does not fit an int, lies outside every map (include/taichislam_hip.h, "coordinates that are not finite").
+// The entry points that take coordinates from a caller without a range gate (Octomap inserts and fusion, point queries, the ray cast) test the quotient x / vs with
+// this BEFORE rnd_i, whose conversion saturates and turns NaN into cell 0; false for NaN.  The integration hot path is range-gated already and does not need it.
+__device__ __forceinline__ bool cell_fits(float q) { return fabsf(q) < 2147483648.0f; }
 __device__ __forceinline__ int sgn_f(float v) { return (0.0f < v) - (v < 0.0f); }     // mapping_common.py:5-7
 
 // x / vs with a loop-invariant divisor.  IEEE division costs ~10 VALU ops on gfx950; with y = RN(1/vs) the sequence

@@ -50,7 +50,9 @@ __device__ __forceinline__ int octo_claim(const OctoDev& M, int s, int b)
 // atomicMax and k_octo_colour lets the winner write (the oracle inserts in index order, so its last writer is the same one).
 __device__ __forceinline__ long long octo_point(const OctoDev& M, int s, float vs, float x, float y, float z, unsigned id1)
 {
-    const int ci = rnd_i(x / vs), cj = rnd_i(y / vs), ck = rnd_i(z / vs);                    // mapping_common.py:252-266
+    const float qx = x / vs, qy = y / vs, qz = z / vs;
+    if (!(cell_fits(qx) && cell_fits(qy) && cell_fits(qz))) return -1;                       // not finite / no int cell: outside the tree (a NaN would convert to cell 0)
+    const int ci = rnd_i(qx), cj = rnd_i(qy), ck = rnd_i(qz);                                // mapping_common.py:252-266
     if (!octo_in_tree(M, ci, cj, ck)) return -1;
     int l; const int b = octo_brick_of(M, ci, cj, ck, &l);
     const int p = octo_claim(M, s, b);
@@ -141,8 +143,9 @@ __global__ void __launch_bounds__(256) k_octo_depth_batch(OctoDev M, OctoBatchAr
             const float mx = ((P.R[0] * px + P.R[1] * py) + P.R[2] * pz) + P.T[0];            // :159
             const float my = ((P.R[3] * px + P.R[4] * py) + P.R[5] * pz) + P.T[1];
             const float mz = ((P.R[6] * px + P.R[7] * py) + P.R[8] * pz) + P.T[2];
-            ci = rnd_i(mx / P.vs); cj = rnd_i(my / P.vs); ck = rnd_i(mz / P.vs);               // process_point :116-119, mapping_common.py:252-266
-            in = octo_in_tree(M, ci, cj, ck);
+            const float qx = mx / P.vs, qy = my / P.vs, qz = mz / P.vs;
+            ci = rnd_i(qx); cj = rnd_i(qy); ck = rnd_i(qz);                                   // process_point :116-119, mapping_common.py:252-266
+            in = cell_fits(qx) && cell_fits(qy) && cell_fits(qz) && octo_in_tree(M, ci, cj, ck);
         }
     }
     const int lane = lane_id();
@@ -233,9 +236,9 @@ __global__ void __launch_bounds__(256) k_octo_fuse(OctoDev S, OctoDev G, int nus
             if (!(c > thres)) continue;                                                      // :181
             int i, j, k; octo_ijk(S, b, l, &i, &j, &k);
             const float p0 = (float)i * vs, p1 = (float)j * vs, p2 = (float)k * vs;
-            int cc[3];
-            for (int a = 0; a < 3; ++a) { const float x = ((Rp[a * 3] * p0 + Rp[a * 3 + 1] * p1) + Rp[a * 3 + 2] * p2) + Rp[9 + a]; cc[a] = rnd_i(x / vs); }   // :182-183
-            if (!octo_in_tree(G, cc[0], cc[1], cc[2])) continue;
+            int cc[3]; bool fits = true;
+            for (int a = 0; a < 3; ++a) { const float x = ((Rp[a * 3] * p0 + Rp[a * 3 + 1] * p1) + Rp[a * 3 + 2] * p2) + Rp[9 + a]; const float q = x / vs; fits = fits && cell_fits(q); cc[a] = rnd_i(q); }   // :182-183
+            if (!fits || !octo_in_tree(G, cc[0], cc[1], cc[2])) continue;
             int gl; const int gb = octo_brick_of(G, cc[0], cc[1], cc[2], &gl);
             const unsigned long long key1 = 1ull + (((unsigned long long)s << 54) | ((unsigned long long)(i + S.hN) << 36) | ((unsigned long long)(j + S.hN) << 18) | (unsigned long long)(k + S.hNz));
             if (pass == 0) {
