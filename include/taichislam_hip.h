@@ -66,7 +66,7 @@ typedef struct {
 enum { TSL_K_VOXELIZE = 0, TSL_K_SORT = 1, TSL_K_RAYS = 2, TSL_K_INTEGRATE = 3, TSL_K_FINALIZE = 4,
        TSL_K_MESH = 5, TSL_K_SEGMENTS = 6, TSL_K_BIN = 7, TSL_K_ESDF = 8, TSL_K_FUSE = 9, TSL_K_REGISTER = 10,
        TSL_K_REGISTER_SCORE = 11, TSL_K_FRONTIER_MARK = 12, TSL_K_FRONTIER_LABEL = 13, TSL_K_FRONTIER_JOIN = 14, TSL_K_FRONTIER_SUM = 15,
-       TSL_K_FRONTIER_EMIT = 16, TSL_K_VIEW_GAIN = 17, TSL_K_COUNT };
+       TSL_K_FRONTIER_EMIT = 16, TSL_K_VIEW_GAIN = 17, TSL_K_ALIGN = 18, TSL_K_ALIGN_POINTS = 19, TSL_K_COUNT };
 
 const char* tsl_version(void);
 const char* tsl_last_error(void);
@@ -368,6 +368,43 @@ int  tsl_tsdf_track_depth(tsl_tsdf* m, const double R0[9], const double T0[3], c
                           double R_out[9], double T_out[3], tsl_track_report* rep);
 int  tsl_tsdf_track_depth_dev(tsl_tsdf* m, const double R0[9], const double T0[3], const tsl_align_cfg* c, const tsl_track_cfg* t, const void* depth_dev,
                               double R_out[9], double T_out[3], tsl_track_report* rep, void* user_stream);
+
+/* ---- scan-to-model alignment (tsl_align_points.hip): a point cloud against the TSDF -- the problem of the section above for sensors whose data is
+ * no pinhole image (a spinning or solid-state lidar, a merged multi-camera cloud, an undistorted depth image): minimise the sum of s(R p_i + T)^2
+ * over the sensor-to-map pose, p_i the points of the cloud in the sensor frame.  R (row-major) / T: the sensor-to-map pose in the frame of
+ * tsl_tsdf_query_points (the active submap's; submap 0 on a global map), given as doubles and rounded to f32 once.  xyz: f32 [n][3],
+ * C-contiguous, 0 <= n <= 2^30.
+ * Definition (all f32, no contraction, in this order).  Visited point k is point k * stride, k < visited = ceil(n /
+ * stride); each lands in exactly one bucket, tested in this order:
+ *   n_gate     x, y or z is not finite, or l2 = (x * x + y * y) + z * z is > dmax2 or < dmin2, with dmax2 = d_max * d_max and dmin2 = d_min * d_min
+ *              formed once in f32 (an l2 that overflows to inf is gated).  Otherwise p[a] = ((R[a][0] * x + R[a][1] * y) + R[a][2] * z) + T[a]
+ *   n_unknown, n_far, n_grad, n_used   as in the section above, with the same 28 products and the same integer sums.
+ * tsl_align_points_cfg: stride >= 1, d_min / d_max (the range gate in metres; 0 = the map's min / max_ray_length), r_max, g_max, huber and flags
+ * bit 0 (counts only) as in tsl_align_cfg.  The overflow bound is that of the section above with the visited points for the visited pixels.
+ * Per-point outputs, each optional (null = not wanted) and indexed by k: bucket[k] (uint8) 0 used, 1 gate, 2 unknown, 3 far, 4 grad; s[k] (f32) the
+ * interpolant at p for used, far and grad, +0.0f for gate and unknown: what a caller needs to drop the points of moving objects before it
+ * integrates the scan.
+ * tsl_tsdf_align_points_linearize issues the queued frames, runs on the handle's stream, waits and returns the 33 integers (and the per-point
+ * outputs).  The device form is ASYNCHRONOUS with the stream ordering of tsl_tsdf_align_linearize_dev: sums_dev (int64[40]), bucket_dev
+ * (uint8[visited]) and s_dev (f32[visited]) are filled on the handle's stream behind every queued frame, after the work queued on `user_stream`,
+ * which then waits for the result.  n = 0 is legal: the sums are zero and nothing is launched.
+ * tsl_tsdf_track_points iterates as tsl_tsdf_track_depth does, with the same tsl_track_cfg (stride[l] is the point stride of level l; the
+ * configuration's own stride is not used) and the same tsl_track_report, statuses and returned pose; an empty cloud ends with status 2.
+ * tsl_tsdf_track_points_dev first makes the handle's stream wait for the work queued on `user_stream`, then runs as the host form and returns
+ * when it is done.  With profiling on, tsl_tsdf_prof_query returns the time of the linearisation kernels alone: TSL_K_ALIGN_POINTS, and TSL_K_ALIGN for
+ * the image form.
+ * TSL_ERR_ARG (the text names the entry point), before anything is launched or written: a null handle / pose / cfg / xyz (with n > 0) / out, a
+ * non-finite pose or parameter, n < 0 or n > 2^30, stride < 1, d_max <= d_min after the defaults, a negative d_min / r_max / g_max / huber, the
+ * overflow bound, the track-configuration errors of the section above. */
+typedef struct { int32_t stride; float d_min, d_max, r_max, g_max, huber; int32_t flags; } tsl_align_points_cfg;
+int  tsl_tsdf_align_points_linearize(tsl_tsdf* m, const double R[9], const double T[3], const tsl_align_points_cfg* c, const float* xyz, int64_t n,
+                                     tsl_align_sums* out, uint8_t* bucket, float* s);
+int  tsl_tsdf_align_points_linearize_dev(tsl_tsdf* m, const double R[9], const double T[3], const tsl_align_points_cfg* c, const void* xyz_dev, int64_t n,
+                                         void* sums_dev, void* bucket_dev, void* s_dev, void* user_stream);
+int  tsl_tsdf_track_points(tsl_tsdf* m, const double R0[9], const double T0[3], const tsl_align_points_cfg* c, const tsl_track_cfg* t, const float* xyz,
+                           int64_t n, double R_out[9], double T_out[3], tsl_track_report* rep);
+int  tsl_tsdf_track_points_dev(tsl_tsdf* m, const double R0[9], const double T0[3], const tsl_align_points_cfg* c, const tsl_track_cfg* t,
+                               const void* xyz_dev, int64_t n, double R_out[9], double T_out[3], tsl_track_report* rep, void* user_stream);
 
 /* ---- map-to-map registration (tsl_register.hip): a TSDF submap against another map, Gauss-Newton on the difference of the two signed distances --
  * minimise the sum of (s(R q_i + T) - t_i)^2 over X = (R, T), q_i the voxels of the source submap near its surface, t_i the values it stores there and

@@ -8,11 +8,11 @@ from . import build as _build
 TSL_OK = 0
 K_VOXELIZE, K_SORT, K_RAYS, K_INTEGRATE, K_FINALIZE, K_MESH, K_SEGMENTS, K_BIN, K_ESDF, K_FUSE, K_REGISTER, K_REGISTER_SCORE = range(12)
 K_FRONTIER_MARK, K_FRONTIER_LABEL, K_FRONTIER_JOIN, K_FRONTIER_SUM, K_FRONTIER_EMIT = range(12, 17)
-K_VIEW_GAIN = 17
+K_VIEW_GAIN, K_ALIGN, K_ALIGN_POINTS = 17, 18, 19
 KERNEL_NAMES = {K_VOXELIZE: "voxelize", K_SORT: "sort", K_RAYS: "build_rays", K_INTEGRATE: "integrate",
                 K_FINALIZE: "finalize", K_MESH: "marching_cubes", K_SEGMENTS: "segments", K_BIN: "bin", K_ESDF: "esdf", K_FUSE: "fuse", K_REGISTER: "register",
                 K_REGISTER_SCORE: "register_score", K_FRONTIER_MARK: "frontier_mark", K_FRONTIER_LABEL: "frontier_label", K_FRONTIER_JOIN: "frontier_join",
-                K_FRONTIER_SUM: "frontier_sum", K_FRONTIER_EMIT: "frontier_emit", K_VIEW_GAIN: "view_gain"}
+                K_FRONTIER_SUM: "frontier_sum", K_FRONTIER_EMIT: "frontier_emit", K_VIEW_GAIN: "view_gain", K_ALIGN: "align", K_ALIGN_POINTS: "align_points"}
 
 
 class TsdfCfg(C.Structure):
@@ -66,6 +66,12 @@ class AlignCfg(C.Structure):
     """tsl_align_cfg (tsl_tsdf_align_linearize, tsl_tsdf_track_depth): a zero K / d_min / d_max / r_max / g_max means the default, huber 0 = off"""
     _fields_ = [("K", C.c_double * 9), ("h", C.c_int32), ("w", C.c_int32), ("stride", C.c_int32), ("d_min", C.c_float), ("d_max", C.c_float),
                 ("r_max", C.c_float), ("g_max", C.c_float), ("huber", C.c_float), ("flags", C.c_int32)]
+
+
+class AlignPointsCfg(C.Structure):
+    """tsl_align_points_cfg (tsl_tsdf_align_points_linearize, tsl_tsdf_track_points): a zero d_min / d_max / r_max / g_max means the default, huber 0 = off"""
+    _fields_ = [("stride", C.c_int32), ("d_min", C.c_float), ("d_max", C.c_float), ("r_max", C.c_float), ("g_max", C.c_float), ("huber", C.c_float),
+                ("flags", C.c_int32)]
 
 
 class AlignSums(C.Structure):
@@ -231,6 +237,10 @@ SIGNATURES = {
     "tsl_pose_retract": (C.c_int, [dp, dp, dp]),
     "tsl_tsdf_track_depth": (C.c_int, [vp, dp, dp, C.POINTER(AlignCfg), C.POINTER(TrackCfg), vp, dp, dp, C.POINTER(TrackReport)]),
     "tsl_tsdf_track_depth_dev": (C.c_int, [vp, dp, dp, C.POINTER(AlignCfg), C.POINTER(TrackCfg), vp, dp, dp, C.POINTER(TrackReport), vp]),
+    "tsl_tsdf_align_points_linearize": (C.c_int, [vp, dp, dp, C.POINTER(AlignPointsCfg), vp, C.c_int64, C.POINTER(AlignSums), vp, vp]),
+    "tsl_tsdf_align_points_linearize_dev": (C.c_int, [vp, dp, dp, C.POINTER(AlignPointsCfg), vp, C.c_int64, vp, vp, vp, vp]),
+    "tsl_tsdf_track_points": (C.c_int, [vp, dp, dp, C.POINTER(AlignPointsCfg), C.POINTER(TrackCfg), vp, C.c_int64, dp, dp, C.POINTER(TrackReport)]),
+    "tsl_tsdf_track_points_dev": (C.c_int, [vp, dp, dp, C.POINTER(AlignPointsCfg), C.POINTER(TrackCfg), vp, C.c_int64, dp, dp, C.POINTER(TrackReport), vp]),
     "tsl_tsdf_register_linearize": (C.c_int, [vp, C.c_int, vp, C.c_int, dp, dp, C.POINTER(RegisterCfg), C.POINTER(AlignSums)]),
     "tsl_tsdf_register_submap": (C.c_int, [vp, C.c_int, vp, C.c_int, dp, dp, C.POINTER(RegisterCfg), C.POINTER(TrackCfg), dp, dp, C.POINTER(TrackReport)]),
     "tsl_tsdf_register_score": (C.c_int, [vp, C.c_int, vp, C.c_int, dp, dp, i32, C.POINTER(RegisterCfg), C.POINTER(RegisterScore), C.POINTER(RegisterGate)]),

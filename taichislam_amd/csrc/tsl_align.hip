@@ -111,8 +111,10 @@ static int align_check(tsl_tsdf* m, const double R[9], const double T[3], const 
 static int align_launch(tsl_tsdf* m, hipStream_t q, const AlignDev& A, const uint16_t* depth, long long* acc)
 {
     TSL_HIP(hipMemsetAsync(acc, 0, AL_SLOTS * sizeof(long long), q));
+    prof_begin(m, TSL_K_ALIGN, q);
     hipLaunchKernelGGL(k_align_linearize, dim3((unsigned)((A.ww + 15) / 16), (unsigned)((A.hh + 15) / 16)), dim3(256), 0, q, m->M,
                        m->cfg.is_global_map ? 0 : m->active, A, depth, acc);
+    prof_end(m, q);
     TSL_HIP(hipGetLastError());
     return TSL_OK;
 }

@@ -100,6 +100,26 @@ def align_config(K=None, shape=(480, 640), stride=1, d_min=None, d_max=None, r_m
     return cfg
 
 
+def align_points_config(stride=1, d_min=None, d_max=None, r_max=None, g_max=None, huber=0.0, counts_only=False):
+    """The tsl_align_points_cfg of DenseTSDF.align_points_linearize / track_points; None = the map's default (passed as 0).  The library checks the values."""
+    cfg = _lib.AlignPointsCfg()
+    cfg.stride = int(stride)
+    for name, v in (("d_min", d_min), ("d_max", d_max), ("r_max", r_max), ("g_max", g_max), ("huber", huber)):
+        if v is not None:
+            setattr(cfg, name, float(v))
+    cfg.flags = 1 if counts_only else 0
+    return cfg
+
+
+def _point_cloud(xyz):
+    """(pointer, n, keep-alive, is_device) of a cloud f32 [n, 3]: a numpy array or a torch CUDA tensor, the forms recast_pcl_to_map accepts"""
+    if _is_device_tensor(xyz):
+        x = xyz.reshape(-1, 3).contiguous().float()
+        return C.c_void_p(x.data_ptr()), int(x.shape[0]), x, True
+    x = np.ascontiguousarray(np.asarray(xyz, dtype=np.float32).reshape(-1, 3))
+    return _vp(x), int(x.shape[0]), x, False
+
+
 ALIGN_SCALE = 2.0 ** -20       # the sums of tsl_align_sums are 2^-20 fixed point
 
 
@@ -1017,6 +1037,61 @@ class DenseTSDF(BaseMap):
                                                        torch.cuda.current_stream(keep.device).cuda_stream))
         else:
             _lib.check(self.L.tsl_tsdf_track_depth(self.h, r, t, C.byref(cfg), C.byref(tc), ptr, ro, to, C.byref(rep)))
+        return Ro.reshape(3, 3), To, _track_info(rep)
+
+    # ---- scan-to-model alignment (tsl_align_points.hip) -------------------------------------------
+    def align_points_linearize(self, xyz, R, T, stride=1, d_min=None, d_max=None, r_max=None, g_max=None, huber=0.0, per_point=False, device=False,
+                               counts_only=False):
+        """The normal equations of aligning a point cloud (f32 [n, 3], sensor frame) to the TSDF at the sensor-to-map pose (R, T) -- in the frame of
+        query_points: Gauss-Newton on s(R p + T) over every stride-th point.  Returns the dict of align_linearize; n_gate counts the points that are
+        not finite or whose range lies outside d_min .. d_max (None = the map's min / max_ray_length).  per_point=True adds `bucket` (uint8 per
+        visited point: 0 used, 1 gate, 2 unknown, 3 far, 4 grad) and `s` (float32: the signed distance at the pose for used, far and grad, 0 for
+        gate and unknown) -- what tells the points of a moving object from the map's.  device=True takes a torch CUDA tensor and returns an int64
+        tensor of 40 on the device (with per_point=True a tuple (sums, bucket, s) of device tensors), asynchronously, ordered with
+        torch.cuda.current_stream (tsl_tsdf_align_points_linearize_dev).  counts_only as in align_linearize."""
+        ptr, n, keep, on_dev = _point_cloud(xyz)
+        cfg = align_points_config(stride, d_min, d_max, r_max, g_max, huber, counts_only)
+        r, t = _dptr(R, 9)[1], _dptr(T, 3)[1]
+        visited = -(-n // cfg.stride) if cfg.stride >= 1 else 0
+        if device:
+            if not on_dev:
+                raise ValueError("align_points_linearize: device=True takes a torch CUDA tensor")
+            torch = _torch()
+            dev = torch.device(f"cuda:{self.device}")
+            out = torch.empty(40, dtype=torch.int64, device=dev)
+            bucket = torch.empty(visited, dtype=torch.uint8, device=dev) if per_point else None
+            sd = torch.empty(visited, dtype=torch.float32, device=dev) if per_point else None
+            _lib.check(self.L.tsl_tsdf_align_points_linearize_dev(self.h, r, t, C.byref(cfg), ptr, n, out.data_ptr(), bucket.data_ptr() if per_point else None,
+                                                                  sd.data_ptr() if per_point else None, torch.cuda.current_stream(dev).cuda_stream))
+            return (out, bucket, sd) if per_point else out
+        if on_dev:
+            keep = keep.cpu().numpy()
+            ptr = _vp(keep)
+        sums = _lib.AlignSums()
+        bucket = np.zeros(visited, np.uint8) if per_point else None
+        sd = np.zeros(visited, np.float32) if per_point else None
+        _lib.check(self.L.tsl_tsdf_align_points_linearize(self.h, r, t, C.byref(cfg), ptr, n, C.byref(sums), _vp(bucket), _vp(sd)))
+        out = align_sums_dict(np.frombuffer(sums, dtype=np.int64))
+        if per_point:
+            out["bucket"], out["s"] = bucket, sd
+        return out
+
+    def track_points(self, xyz, R, T, levels=((8, 4), (4, 4), (1, 6)), min_step=1e-4, damping=0.0, min_used=None, **gates):
+        """Refine the sensor-to-map pose (R, T) of a point cloud against the TSDF: track_depth for a cloud.  levels: up to 4 (point stride, iterations).
+        Returns (R 3 x 3, T 3, info) shaped as track_depth's.  xyz: a numpy array or a torch CUDA tensor (ordered with torch.cuda.current_stream);
+        gates: the d_min / d_max / r_max / g_max / huber of align_points_linearize."""
+        ptr, n, keep, on_dev = _point_cloud(xyz)
+        cfg = align_points_config(1, **gates)
+        tc = _track_config(levels, min_step, damping, min_used)
+        r, t = _dptr(R, 9)[1], _dptr(T, 3)[1]
+        Ro, To, ro, to = _pose_out()
+        rep = _lib.TrackReport()
+        if on_dev:
+            torch = _torch()
+            _lib.check(self.L.tsl_tsdf_track_points_dev(self.h, r, t, C.byref(cfg), C.byref(tc), ptr, n, ro, to, C.byref(rep),
+                                                        torch.cuda.current_stream(keep.device).cuda_stream))
+        else:
+            _lib.check(self.L.tsl_tsdf_track_points(self.h, r, t, C.byref(cfg), C.byref(tc), ptr, n, ro, to, C.byref(rep)))
         return Ro.reshape(3, 3), To, _track_info(rep)
 
     # ---- map-to-map registration (tsl_register.hip, DESIGN.md section 4.9) -------------------------------------------------
