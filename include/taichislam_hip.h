@@ -329,11 +329,16 @@ int  tsl_tsdf_render_view_dev(tsl_tsdf* m, const double R[9], const double T[3],
  *              py = ((float)j - cy) * dep / fy, pz = dep and p[a] = ((R[a][0] * px + R[a][1] * py) + R[a][2] * pz) + T[a]
  *   n_unknown  the sample at p is not KNOWN in the sense of tsl_tsdf_render_view (8 corners in the volume, in allocated bricks and observed, p
  *              finite).  Otherwise s = the trilinear interpolant, g = its gradient per metre (the expressions of tsl_esdf_query_points mode 1)
- *   n_far      |s| > r_max
- *   n_grad     gg = (g0 * g0 + g1 * g1) + g2 * g2 is 0 or > g_max * g_max
+ *   n_far      not |s| <= r_max: |s| > r_max, or s is a NaN
+ *   n_grad     gg = (g0 * g0 + g1 * g1) + g2 * g2 is not in (0, g_max * g_max]: 0, above it, or a NaN
  *   n_used     c = p x g, J = (g0, g1, g2, c0, c1, c2), wgt = huber > 0 && |s| > huber ? huber / |s| : 1, wJ[a] = wgt * J[a]; the 28 products
  *              H_ab = wJ[a] * J[b] (a <= b, row-major upper triangle), b_a = wJ[a] * s, e = (wgt * s) * s
  * Every product x is added as the integer rint(x * 2^20) (round half to even) into an int64 sum, so the sums are the same for any schedule.
+ * Stored values that are not finite (tsl_tsdf_import_sparse writes any f16 bit pattern; a submap from another robot may hold one): a NaN or inf
+ * corner makes the interpolant or the gradient of its cell a NaN or an inf (0 * inf is a NaN), and such a sample is far or grad, never used -- no
+ * value that is not finite reaches a product, so the sums stay defined and the overflow refusal holds.  The per-point s of a far sample whose
+ * interpolant is a NaN is that NaN as it stands (which NaN is not specified).  The readers that return floats (tsl_tsdf_render_view, the ESDF
+ * queries, the meshing) pass such a value through.
  * tsl_align_cfg: K row-major intrinsics (all 9 zero = the map's depth intrinsics), stride >= 1, d_min / d_max (0 = the map's min / max_ray_length),
  * r_max (0 = internal_voxels * voxel, the depth of the negative band), g_max (0 = 4), huber (0 = off), flags bit 0 = counts only: the
  * products and their reduction are left out, H, b and e are 0 (what the gathers alone cost: the A/B switch of tools/bench_track.py; a tracker needs 0).
@@ -416,14 +421,15 @@ int  tsl_tsdf_track_points_dev(tsl_tsdf* m, const double R0[9], const double T0[
  * coordinates, given as doubles and rounded to f32 once.
  * Definition (all f32, no contraction, in this order).  Visited: the observed voxels of the source submap whose indices (i, j, k)
  * are each divisible by stride; unobserved voxels are neither visited nor counted.  Each visited voxel lands in exactly one bucket, tested in this order:
- *   n_gate     w = f16 weight fails w >= w_min, or fabsf(t) > band, t the stored f16 TSDF value.  Otherwise q = ((float)i * voxel, (float)j * voxel,
+ *   n_gate     not (w >= w_min && fabsf(t) <= band), w the stored f16 weight, t the stored f16 TSDF value: a NaN weight or value is gated.  Otherwise q = ((float)i * voxel, (float)j * voxel,
  *              (float)k * voxel) and p[a] = ((R[a][0] * q0 + R[a][1] * q1) + R[a][2] * q2) + T[a]
  *   n_unknown  the sample of dst at p is not KNOWN in the sense of tsl_tsdf_render_view (8 corners in the volume, in allocated bricks of dst_sid and
  *              observed, p finite).  Otherwise s = the trilinear interpolant, g = its gradient per metre (tsl_esdf_query_points mode 1)
- *   n_far      |s| > r_max
- *   n_grad     gg = (g0 * g0 + g1 * g1) + g2 * g2 is 0 or > g_max * g_max
+ *   n_far      not |s| <= r_max: |s| > r_max, or s is a NaN
+ *   n_grad     gg = (g0 * g0 + g1 * g1) + g2 * g2 is not in (0, g_max * g_max]: 0, above it, or a NaN
  *   n_used     r = s - t, c = p x g, J = (g0, g1, g2, c0, c1, c2), wgt = huber > 0 && |r| > huber ? huber / |r| : 1, wJ[a] = wgt * J[a]; the 28 products
  *              H_ab = wJ[a] * J[b] (a <= b, row-major upper triangle), b_a = wJ[a] * r, e = (wgt * r) * r
+ * As in the alignment, a stored value of dst that is not finite makes its cells' samples far or grad, and one of src is gated: none reaches a product.
  * Every product x is added as the integer rint(x * 2^20) into an int64 sum; the result is a tsl_align_sums, the same 33 integers in the same order,
  * so tsl_align_solve and tsl_pose_retract serve unchanged (the step is the left twist p <- p + v + omega x p).
  * tsl_register_cfg: stride 1, 2, 4, 8 or 16; w_min (0 = every weight passes); band (0 = 2 * voxel); r_max (0 = internal_voxels * voxel of dst); g_max

@@ -8,8 +8,8 @@
 //   gate     d == 0, (float)d > d_max * 1000 or (float)d < d_min * 1000 (the comparisons of k_voxelize_depth, tsl_tsdf.hip); otherwise
 //            dep = (float)d / 1000, px = ((float)i - cx) * dep / fx, py = ((float)j - cy) * dep / fy, pz = dep, p[a] = ((R[a][0] px + R[a][1] py) + R[a][2] pz) + T[a]
 //   unknown  the sample at p is not KNOWN (section 4.7); otherwise s = tri_value, g = tri_grad / vs
-//   far      |s| > r_max
-//   grad     gg = (g0 g0 + g1 g1) + g2 g2 is 0 or > g_max * g_max
+//   far      not |s| <= r_max (a NaN s, from a stored value that is not finite, is far)
+//   grad     gg = (g0 g0 + g1 g1) + g2 g2 is not in (0, g_max * g_max]
 //   used     c = p x g, J = (g, c), wgt = huber > 0 && |s| > huber ? huber / |s| : 1, wJ = wgt J; the 28 products H_ab = wJ[a] J[b] (a <= b), b_a = wJ[a] s,
 //            e = (wgt s) s
 // Every product x is added as the integer rint(x * 2^20) (round half to even) into int64 sums: integer sums do not depend on the order of

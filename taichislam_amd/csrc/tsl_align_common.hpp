@@ -51,11 +51,11 @@ __device__ __forceinline__ int al_sample(const float p[3], const MapDev& M, cons
     if (!(isfinite(p[0]) && isfinite(p[1]) && isfinite(p[2]) && tsdf_read_cell(M, T, b[0], b[1], b[2], V))) return AL_UNKNOWN;
     const float f0 = u[0] - (float)b[0], f1 = u[1] - (float)b[1], f2 = u[2] - (float)b[2];
     *s = tri_value(V, f0, f1, f2);
-    if (fabsf(*s) > r_max) return AL_FAR;
+    if (!(fabsf(*s) <= r_max)) return AL_FAR;                     // a NaN interpolant (a stored value that is not finite) is far
     tri_grad(V, f0, f1, f2, &g[0], &g[1], &g[2]);
     g[0] = g[0] / vs; g[1] = g[1] / vs; g[2] = g[2] / vs;
     const float gg = (g[0] * g[0] + g[1] * g[1]) + g[2] * g[2];
-    return (gg == 0.0f || gg > gm2) ? AL_GRAD : AL_USED;
+    return (gg > 0.0f && gg <= gm2) ? AL_USED : AL_GRAD;          // a NaN or inf gradient is grad: no value that is not finite reaches a product
 }
 
 // the robust weight of the residual r

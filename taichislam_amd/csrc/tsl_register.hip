@@ -6,11 +6,11 @@
 // Definition (tests/register_ref.py restates it in numpy and every integer must equal it).  All f32, no contraction, in the
 // written order.  Visited: the observed voxels (obs > 0) of the source submap whose indices (i, j, k) are each divisible by stride (1, 2, 4, 8 or 16).
 // A visited voxel with the stored word tw falls into exactly one bucket:
-//   gate     w = h2f(tw >> 16) fails w >= w_min, or |t| > band, t = h2f(tw & 0xffff); otherwise q = ((float)i vs, (float)j vs, (float)k vs),
+//   gate     w = h2f(tw >> 16) fails w >= w_min, or not |t| <= band (a NaN is gated), t = h2f(tw & 0xffff); otherwise q = ((float)i vs, (float)j vs, (float)k vs),
 //            p[a] = ((R[a][0] q0 + R[a][1] q1) + R[a][2] q2) + T[a]
 //   unknown  the destination's sample at p is not KNOWN (section 4.7); otherwise s = tri_value, g = tri_grad / vs
-//   far      |s| > r_max
-//   grad     gg = (g0 g0 + g1 g1) + g2 g2 is 0 or > g_max * g_max
+//   far      not |s| <= r_max (a NaN s, from a stored value that is not finite, is far)
+//   grad     gg = (g0 g0 + g1 g1) + g2 g2 is not in (0, g_max * g_max]
 //   used     r = s - t, c = p x g, J = (g, c), wgt = huber > 0 && |r| > huber ? huber / |r| : 1, wJ = wgt J; the 28 products H_ab = wJ[a] J[b] (a <= b),
 //            b_a = wJ[a] r, e = (wgt r) r, each added as rint(x * 2^20) into int64 sums (al_fix): the 33 integers of tsl_align_sums.
 //

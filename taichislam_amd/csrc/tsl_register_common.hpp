@@ -50,7 +50,7 @@ __device__ __forceinline__ void rg_scan_row(const MapDev& S, const RegisterDev& 
         const bool seen = row && (int8_t)((obw[r >> 2] >> ((r & 3) * 8)) & 0xffu) > 0;
         const uint32_t tw = tww[r];
         const float w = h2f((h16)(tw >> 16)), t = h2f((h16)(tw & 0xffffu));
-        f(r, seen, seen && (w >= A.w_min) && !(fabsf(t) > A.band), tw);
+        f(r, seen, seen && (w >= A.w_min) && (fabsf(t) <= A.band), tw);      // a NaN weight or value is gated
     }
 }
 

@@ -23,9 +23,10 @@ def defaults(vs, internal_voxels, voxel_scale, w_min=0.0, band=0.0, r_max=0.0, g
                 g_max=F32(g_max) if g_max else F32(4.0), huber=F32(huber))
 
 
-def linearize(src, R, T, stride, vs, grid, w_min, band, r_max, g_max, huber=0.0, order=None):
+def linearize(src, R, T, stride, vs, grid, w_min, band, r_max, g_max, huber=0.0, order=None, addends=None):
     """The 33 integers of one linearisation.  src = source(export); R, T float64 (rounded to f32 once); grid = (val, known, lo) of the destination;
-    w_min / band / r_max / g_max / huber are the values after the defaults; order: a permutation of the source's voxels (the sums do not depend on it)."""
+    w_min / band / r_max / g_max / huber are the values after the defaults; order: a permutation of the source's voxels (the sums do not depend on it);
+    addends: as in track_ref.points."""
     assert stride in STRIDES
     idx, t, w = src
     if order is not None:
@@ -36,11 +37,11 @@ def linearize(src, R, T, stride, vs, grid, w_min, band, r_max, g_max, huber=0.0,
     lattice = ((idx % stride) == 0).all(1)
     idx, t, w = idx[lattice], t[lattice], w[lattice]
     with np.errstate(invalid="ignore", over="ignore", divide="ignore"):
-        gate = ~(w >= w_min) | (np.abs(t) > band)
+        gate = ~((w >= w_min) & (np.abs(t) <= band))      # a NaN weight or value is gated
         idx, t = idx[~gate], t[~gate]
         q = idx.astype(F32) * vs
         p = np.stack([((R[a, 0] * q[:, 0] + R[a, 1] * q[:, 1]) + R[a, 2] * q[:, 2]) + T[a] for a in range(3)], 1).astype(F32)
-    return tr.points(p, t, vs, grid, r_max, g_max, huber, n_gate=gate.sum())
+    return tr.points(p, t, vs, grid, r_max, g_max, huber, n_gate=gate.sum(), addends=addends)
 
 
 def visited(src, stride):

@@ -19,7 +19,7 @@ def _gated(src, stride, w_min, band):
     idx, t, w = src
     lattice = ((idx % stride) == 0).all(1)
     with np.errstate(invalid="ignore"):
-        gate = ~(w[lattice] >= F32(w_min)) | (np.abs(t[lattice]) > F32(band))
+        gate = ~((w[lattice] >= F32(w_min)) & (np.abs(t[lattice]) <= F32(band)))
     return lattice, ~gate
 
 
@@ -68,11 +68,11 @@ def score(src, R, T, stride, vs, grid, w_min, band, r_max, g_max, huber=0.0, cou
                           for a in range(3)], 2).astype(F32).reshape(c * m, 3)
             s, kn, g = rv.sample(p, vs, val, known, lo)
             g = (g / vs).astype(F32)
-            far = kn & (np.abs(s) > r_max)
+            far = kn & ~(np.abs(s) <= r_max)
             gg = (g[:, 0] * g[:, 0] + g[:, 1] * g[:, 1]) + g[:, 2] * g[:, 2]
-            bad = kn & ~far & ((gg == 0) | (gg > gm2))
+            bad = kn & ~far & ~((gg > 0) & (gg <= gm2))
             used = kn & ~far & ~bad
-            r = (s - np.tile(t, c)).astype(F32)
+            r = np.where(used, s - np.tile(t, c), F32(0)).astype(F32)      # only a used sample's residual reaches fix()
             e = np.where(used, tr.fix((tr.robust_weight(r, huber) * r) * r), 0)
             sl = slice(a0, a0 + c)
             out["e"][sl] = e.reshape(c, m).sum(1)

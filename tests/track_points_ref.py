@@ -38,16 +38,16 @@ def classify(p, vs, grid, r_max, g_max):
         s, kn, g = rv.sample(p, vs, val, known, lo)
         g = (g / vs).astype(F32)
         gg = (g[:, 0] * g[:, 0] + g[:, 1] * g[:, 1]) + g[:, 2] * g[:, 2]
-        far = np.abs(s) > r_max
-        bad = (gg == 0) | (gg > g_max * g_max)
+        far = ~(np.abs(s) <= r_max)
+        bad = ~((gg > 0) & (gg <= g_max * g_max))
     bucket = np.where(~kn, UNKNOWN, np.where(far, FAR, np.where(bad, GRAD, USED))).astype(np.uint8)
     return bucket, np.where(kn, s, F32(0.0)).astype(F32)
 
 
-def linearize_points(xyz, R, T, stride, vs, grid, d_min=0.3, d_max=5.0, r_max=0.4, g_max=4.0, huber=0.0, order=None):
+def linearize_points(xyz, R, T, stride, vs, grid, d_min=0.3, d_max=5.0, r_max=0.4, g_max=4.0, huber=0.0, order=None, addends=None):
     """(the 33 integers, bucket uint8 [visited], s f32 [visited]) of one linearisation.  xyz f32 [n, 3] in the sensor frame; R, T float64 (rounded
     to f32 once); grid = (val, known, lo); the gates are the values after the defaults; order: a permutation of the visited points (the sums do not
-    depend on it; bucket and s follow it)."""
+    depend on it; bucket and s follow it); addends: as in track_ref.points."""
     xyz = np.ascontiguousarray(np.asarray(xyz, F32).reshape(-1, 3))[::stride]
     if order is not None:
         xyz = xyz[order]
@@ -56,7 +56,7 @@ def linearize_points(xyz, R, T, stride, vs, grid, d_min=0.3, d_max=5.0, r_max=0.
     s = np.zeros(xyz.shape[0], F32)
     q = p[~gate]
     bucket[~gate], s[~gate] = classify(q, vs, grid, r_max, g_max)
-    sums = tr.points(q, np.zeros(q.shape[0], F32), vs, grid, r_max, g_max, huber, n_gate=int(gate.sum()))
+    sums = tr.points(q, np.zeros(q.shape[0], F32), vs, grid, r_max, g_max, huber, n_gate=int(gate.sum()), addends=addends)
     assert [int((bucket == c).sum()) for c in (USED, GATE, UNKNOWN, FAR, GRAD)] == sums[tr.I_USED:].tolist()
     return sums, bucket, s
 

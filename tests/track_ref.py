@@ -20,7 +20,9 @@ def visited(h, w, stride):
 
 
 def fix(x):
-    """Q(x) = (int64) rint((double)x * 2^20), round half to even"""
+    """Q(x) = (int64) rint((double)x * 2^20), round half to even.  x must be finite: the buckets keep a value that is not finite from every product
+    (the conversion of a NaN to an integer is undefined)."""
+    assert np.isfinite(x).all(), "a product that is not finite reached fix()"
     return np.rint(np.asarray(x, F32).astype(np.float64) * SCALE).astype(np.int64)
 
 
@@ -31,10 +33,10 @@ def robust_weight(r, huber):
     return np.where((huber > 0) & (a_r > huber), huber / np.where(a_r > 0, a_r, one), one).astype(F32)
 
 
-def points(p, t, vs, grid, r_max, g_max, huber, n_gate=0):
+def points(p, t, vs, grid, r_max, g_max, huber, n_gate=0, addends=None):
     """What the alignment and the registration share: the 33 integers of the map-frame points p f32 [n, 3] against the target values t f32 [n] (zeros
     for the alignment): each point is unknown, far, grad or used, a used one adds its 28 products with the residual r = s - t.  n_gate: the
-    caller's gate count, which it formed on the way to p."""
+    caller's gate count, which it formed on the way to p.  addends: a list that receives the 28 int64 arrays [n_used] the sums are formed from."""
     val, known, lo = grid
     vs, r_max, g_max, huber = F32(vs), F32(r_max), F32(g_max), F32(huber)
     gm2 = g_max * g_max
@@ -44,11 +46,11 @@ def points(p, t, vs, grid, r_max, g_max, huber, n_gate=0):
         s, kn, g = rv.sample(p, vs, val, known, lo)
         out[I_UNKNOWN] = (~kn).sum()
         p, s, t, g = p[kn], s[kn], t[kn], (g[kn] / vs).astype(F32)
-        far = np.abs(s) > r_max
+        far = ~(np.abs(s) <= r_max)                       # a NaN interpolant is far
         out[I_FAR] = far.sum()
         p, s, t, g = p[~far], s[~far], t[~far], g[~far]
         gg = (g[:, 0] * g[:, 0] + g[:, 1] * g[:, 1]) + g[:, 2] * g[:, 2]
-        bad = (gg == 0) | (gg > gm2)
+        bad = ~((gg > 0) & (gg <= gm2))                   # a NaN gradient is grad
         out[I_GRAD] = bad.sum()
         p, s, t, g = p[~bad], s[~bad], t[~bad], g[~bad]
         out[I_USED] = s.size
@@ -59,21 +61,18 @@ def points(p, t, vs, grid, r_max, g_max, huber, n_gate=0):
         J = [g[:, 0], g[:, 1], g[:, 2], c0, c1, c2]
         wgt = robust_weight(r, huber)
         wJ = [wgt * x for x in J]
-        k = 0
-        for a in range(6):
-            for b in range(a, 6):
-                out[k] = fix(wJ[a] * J[b]).sum()
-                k += 1
-        for a in range(6):
-            out[21 + a] = fix(wJ[a] * r).sum()
-        out[I_E] = fix((wgt * r) * r).sum()
+        q = [fix(wJ[a] * J[b]) for a in range(6) for b in range(a, 6)] + [fix(wJ[a] * r) for a in range(6)] + [fix((wgt * r) * r)]
+        for k in range(28):
+            out[k] = q[k].sum()
+        if addends is not None:
+            addends.extend(q)
     return out
 
 
-def linearize(depth, R, T, K, stride, vs, grid, d_min=0.3, d_max=5.0, r_max=0.4, g_max=4.0, huber=0.0, order=None):
+def linearize(depth, R, T, K, stride, vs, grid, d_min=0.3, d_max=5.0, r_max=0.4, g_max=4.0, huber=0.0, order=None, addends=None):
     """The 33 integers of one linearisation.  depth uint16 [h, w]; R, T float64 (rounded to f32 once); K 9 values; grid = (val, known, lo);
     d_min / d_max / r_max / g_max / huber are the values after the defaults (r_max and g_max are rounded to f32 as the configuration holds them);
-    order: a permutation of the visited pixels (the sums do not depend on it)."""
+    order: a permutation of the visited pixels (the sums do not depend on it); addends: as in points."""
     depth = np.asarray(depth)
     assert depth.dtype == np.uint16 and depth.ndim == 2
     h, w = depth.shape
@@ -97,7 +96,7 @@ def linearize(depth, R, T, K, stride, vs, grid, d_min=0.3, d_max=5.0, r_max=0.4,
         py = (j.astype(F32) - cy) * dep / fy
         pz = dep
         p = np.stack([((R[a, 0] * px + R[a, 1] * py) + R[a, 2] * pz) + T[a] for a in range(3)], 1).astype(F32)
-    return points(p, np.zeros(p.shape[0], F32), vs, grid, r_max, g_max, huber, n_gate=gate.sum())
+    return points(p, np.zeros(p.shape[0], F32), vs, grid, r_max, g_max, huber, n_gate=gate.sum(), addends=addends)
 
 
 def system(sums, damping=0.0):
