@@ -66,7 +66,8 @@ typedef struct {
 enum { TSL_K_VOXELIZE = 0, TSL_K_SORT = 1, TSL_K_RAYS = 2, TSL_K_INTEGRATE = 3, TSL_K_FINALIZE = 4,
        TSL_K_MESH = 5, TSL_K_SEGMENTS = 6, TSL_K_BIN = 7, TSL_K_ESDF = 8, TSL_K_FUSE = 9, TSL_K_REGISTER = 10,
        TSL_K_REGISTER_SCORE = 11, TSL_K_FRONTIER_MARK = 12, TSL_K_FRONTIER_LABEL = 13, TSL_K_FRONTIER_JOIN = 14, TSL_K_FRONTIER_SUM = 15,
-       TSL_K_FRONTIER_EMIT = 16, TSL_K_VIEW_GAIN = 17, TSL_K_ALIGN = 18, TSL_K_ALIGN_POINTS = 19, TSL_K_COUNT };
+       TSL_K_FRONTIER_EMIT = 16, TSL_K_VIEW_GAIN = 17, TSL_K_ALIGN = 18, TSL_K_ALIGN_POINTS = 19, TSL_K_PATH_SCORE = 20,
+       TSL_K_COUNT };
 
 const char* tsl_version(void);
 const char* tsl_last_error(void);
@@ -289,6 +290,45 @@ int  tsl_esdf_query_points(tsl_tsdf* m, int mode, float unknown_value, const flo
                            float* dist, float* grad, uint8_t* status);
 int  tsl_esdf_query_points_dev(tsl_tsdf* m, int mode, float unknown_value, const void* xyz_dev, int64_t n,
                                void* dist_dev, void* grad_dev, void* status_dev, void* user_stream);
+/* batches of candidate paths scored against the ESDF in one launch (tsl_path_score.hip): which of these motions is free, how close does each come,
+ * what does each cost.  Read-only, one wave per path.  Definition (tests/path_score_ref.py restates it in numpy bit for bit):
+ *   Inputs.  waypoints f32 [n][K][3] in the frame of tsl_esdf_query_points; lengths int32 [n], nullable (NULL: every path has K waypoints), each in
+ *     1 .. K -- the waypoints behind a path's length are never read and may hold anything; sub >= 1 sub-samples per segment; radius, margin f32, finite
+ *     and >= 0; mode 0 / 1 and unknown_value as in tsl_esdf_query_points; flags below.
+ *   Samples.  A path of length L has S = (L - 1) * sub + 1 samples j = 0 .. S-1; seg = j / sub, m = j % sub.  For m == 0 the sample is waypoint seg
+ *     itself, bit for bit; otherwise p = a + t * (b - a) per component with t = (float)m / (float)sub, a = waypoint seg, b = waypoint seg + 1 (all f32,
+ *     no contraction, correctly rounded division).  S_max = (K - 1) * sub + 1.
+ *   Value and status of a sample: exactly what tsl_esdf_query_points returns for p in that mode, except that a sample of status 0 whose value is NaN,
+ *     or that reads a voxel whose TSDF is NaN (one that came in through tsl_tsdf_import_sparse: the query reports sign(NaN) = 0 times the magnitude
+ *     for it, so the value alone does not show it), counts as status 1 everywhere below.
+ *   Classes.  hit: status 0 and d < radius; unknown: status 1; outside: status 2.  A sample BLOCKS when it is a hit, when it is unknown and flags & 2,
+ *     or when it is outside and flags & 4.  first_stop = the least blocking index, or -1.
+ *   Counted samples.  flags & 1 clear: every sample.  flags & 1 set (stop at the first blocking sample): the samples 0 .. first_stop inclusive; all of
+ *     them when nothing blocks.
+ *   tsl_path_score (40 bytes, one per path): n_samples, the counted samples; first_stop; n_hit, n_unknown, n_outside over the counted samples; argmin and
+ *     min_dist over the counted samples of status 0: the minimum of the pair (key(d), j) in lexicographic order, key(d) = the monotone uint32 image of
+ *     the float's bits (bits ^ 0xffffffff when the sign bit is set, else bits ^ 0x80000000: -0.0 sorts before +0.0, ties go to the lowest index),
+ *     min_dist = the value at argmin bit for bit; without such a sample argmin = -1 and min_dist = +inf.  short_update: 0, or 0x80 when the values come
+ *     from an update that stopped before converging (the flag of tsl_esdf_query_points; only the device form can see one).  cost: the sum over the
+ *     counted samples of status 0 with c > 0 of (int64)(int32)(c * 1048576.0f), truncated toward zero, c = fminf(rm - d, 1024.0f), rm = radius + margin
+ *     rounded to f32 once on the host: a 2^-20 fixed point, order-free, at most 2^30 per term.
+ *   Optional per-sample outputs, each nullable on its own: sample_dist f32 [n][S_max] and sample_status u8 [n][S_max].  A counted sample gets the
+ *     query's dist and status (0 / 1 / 2, without the 0x80 flag, which is in the record; a NaN-valued sample: unknown_value and 1); every other entry of
+ *     the row gets unknown_value and 0xff.
+ * TSL_ERR_ARG, before anything is launched or written: whatever tsl_esdf_query_points refuses (no update since the map was created, reset or imported;
+ * the active submap changed; a bad mode); null waypoints or out with n > 0; n outside 0 .. 2^20; K outside 1 .. 4096; sub outside 1 .. 256; S_max > 2^20;
+ * n * S_max >= 2^31 with a per-sample output; radius or margin negative or not finite; flags with bits other than 1, 2, 4; and, in the host form, a
+ * length outside 1 .. K -- the device form cannot look and CLAMPS every length into 1 .. K.  n = 0 does nothing.
+ * The host form copies in through the handle's staging buffer and waits for the updates in flight first (never sees a short one); the device form is
+ * ASYNCHRONOUS and ordered like tsl_esdf_query_points_dev (lengths_dev nullable; out_dev holds n records, as int32 [n][10]).  out_dev
+ * must be aligned to 8 bytes (the int64 cost lies at offset 32 of the 40-byte record), waypoints_dev, lengths_dev and sample_dist_dev to 4.  With
+ * profiling on, tsl_tsdf_prof_query(m, TSL_K_PATH_SCORE) returns the time of the kernel alone. */
+typedef struct { int32_t n_samples, first_stop, n_hit, n_unknown, n_outside, argmin; float min_dist; int32_t short_update; int64_t cost; } tsl_path_score;
+int  tsl_esdf_score_paths(tsl_tsdf* m, int mode, float unknown_value, const float* waypoints, const int32_t* lengths, int64_t n, int32_t K, int32_t sub,
+                          float radius, float margin, int32_t flags, tsl_path_score* out, float* sample_dist, uint8_t* sample_status);
+int  tsl_esdf_score_paths_dev(tsl_tsdf* m, int mode, float unknown_value, const void* waypoints_dev, const void* lengths_dev, int64_t n, int32_t K,
+                              int32_t sub, float radius, float margin, int32_t flags, void* out_dev, void* sample_dist_dev, void* sample_status_dev,
+                              void* user_stream);
 
 /* ---- view rendering (tsl_render.hip): what a camera at a pose would see of the TSDF -- depth, normal and colour per pixel.  It stands beside
  * BaseMap.raycast (mapping_common.py:165-178; tsl_tsdf_query_raycast above), which steps a whole voxel at a time and returns the last stepped

@@ -8,11 +8,12 @@ from . import build as _build
 TSL_OK = 0
 K_VOXELIZE, K_SORT, K_RAYS, K_INTEGRATE, K_FINALIZE, K_MESH, K_SEGMENTS, K_BIN, K_ESDF, K_FUSE, K_REGISTER, K_REGISTER_SCORE = range(12)
 K_FRONTIER_MARK, K_FRONTIER_LABEL, K_FRONTIER_JOIN, K_FRONTIER_SUM, K_FRONTIER_EMIT = range(12, 17)
-K_VIEW_GAIN, K_ALIGN, K_ALIGN_POINTS = 17, 18, 19
+K_VIEW_GAIN, K_ALIGN, K_ALIGN_POINTS, K_PATH_SCORE = 17, 18, 19, 20
 KERNEL_NAMES = {K_VOXELIZE: "voxelize", K_SORT: "sort", K_RAYS: "build_rays", K_INTEGRATE: "integrate",
                 K_FINALIZE: "finalize", K_MESH: "marching_cubes", K_SEGMENTS: "segments", K_BIN: "bin", K_ESDF: "esdf", K_FUSE: "fuse", K_REGISTER: "register",
                 K_REGISTER_SCORE: "register_score", K_FRONTIER_MARK: "frontier_mark", K_FRONTIER_LABEL: "frontier_label", K_FRONTIER_JOIN: "frontier_join",
-                K_FRONTIER_SUM: "frontier_sum", K_FRONTIER_EMIT: "frontier_emit", K_VIEW_GAIN: "view_gain", K_ALIGN: "align", K_ALIGN_POINTS: "align_points"}
+                K_FRONTIER_SUM: "frontier_sum", K_FRONTIER_EMIT: "frontier_emit", K_VIEW_GAIN: "view_gain", K_ALIGN: "align", K_ALIGN_POINTS: "align_points",
+                K_PATH_SCORE: "path_score"}
 
 
 class TsdfCfg(C.Structure):
@@ -148,6 +149,12 @@ class ViewGain(C.Structure):
                 ("n_range", C.c_int32), ("n_cut", C.c_int32), ("n_frontier", C.c_int32), ("reserved_", C.c_int32 * 4)]
 
 
+class PathScore(C.Structure):
+    """tsl_path_score: 40 bytes per path, the layout of PATH_SCORE_DTYPE"""
+    _fields_ = [("n_samples", C.c_int32), ("first_stop", C.c_int32), ("n_hit", C.c_int32), ("n_unknown", C.c_int32), ("n_outside", C.c_int32),
+                ("argmin", C.c_int32), ("min_dist", C.c_float), ("short_update", C.c_int32), ("cost", C.c_int64)]
+
+
 class TslError(RuntimeError):
     pass
 
@@ -229,6 +236,8 @@ SIGNATURES = {
     "tsl_esdf_slice_dev": (C.c_int, [vp, C.POINTER(vp), C.POINTER(vp), pi32]),
     "tsl_esdf_query_points": (C.c_int, [vp, C.c_int, f32, vp, i64, vp, vp, vp]),
     "tsl_esdf_query_points_dev": (C.c_int, [vp, C.c_int, f32, vp, i64, vp, vp, vp, vp]),
+    "tsl_esdf_score_paths": (C.c_int, [vp, C.c_int, f32, vp, vp, i64, i32, i32, f32, f32, i32, vp, vp, vp]),
+    "tsl_esdf_score_paths_dev": (C.c_int, [vp, C.c_int, f32, vp, vp, i64, i32, i32, f32, f32, i32, vp, vp, vp, vp]),
     "tsl_tsdf_render_view": (C.c_int, [vp, dp, dp, C.POINTER(ViewCfg), vp, vp, vp, vp]),
     "tsl_tsdf_render_view_dev": (C.c_int, [vp, dp, dp, C.POINTER(ViewCfg), vp, vp, vp, vp, vp]),
     "tsl_tsdf_align_linearize": (C.c_int, [vp, dp, dp, C.POINTER(AlignCfg), vp, C.POINTER(AlignSums)]),

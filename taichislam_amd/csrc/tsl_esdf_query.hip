@@ -3,22 +3,13 @@
 // read-only gathers through the brick table, no LDS, no atomics.
 //
 // A voxel V(i,j,k) of the submap the ESDF was last updated for is KNOWN when it lies in the volume, its brick is allocated and obs > 0; its
-// value is exactly what k_esdf_export reports (esdf_value below).  Mode 0 reads the nearest voxel (rnd_i(x / vs), as k_query_points does);
+// value is exactly what k_esdf_export reports (esdf_value, tsl_esdf_sample.hpp).  Mode 0 reads the nearest voxel (rnd_i(x / vs), as k_query_points does);
 // mode 1 interpolates the 8 corners of the cell trilinearly in a fixed f32 order and returns the gradient of that interpolant, so that
 // tests/esdf_query_ref.py can restate it bit for bit in numpy.  Status per query: 0 ok, 1 a needed voxel is unknown, 2 a needed voxel is
 // outside the volume (or a coordinate is not finite); | 0x80 when the values come from an update that stopped before converging.
-#include "tsl_interp.hpp"      // lerp_f, cell_floor, the corner bricks and the interpolant: shared with tsl_render.hip
+#include "tsl_esdf_sample.hpp"      // esdf_sample: the look-up, the value and the interpolant, shared with tsl_path_score.hip
 
 namespace tsl {
-
-#define EQ_UNKNOWN 1
-#define EQ_OUTSIDE 2
-#define EQ_SHORT 0x80
-
-// the value k_esdf_export reports for an observed voxel (tsl_esdf.hip, k_esdf_export): the TSDF inside the band, elsewhere its sign times the
-// relaxed magnitude (max_dist where the voxel was not observed at the last update)
-__device__ __forceinline__ float esdf_value(float t, float e, float gamma, float max_dist)
-{ return fabsf(t) < gamma ? t : (float)sgn_f(t) * (e != e ? max_dist : fabsf(e)); }
 
 template <int MODE>
 __global__ void __launch_bounds__(256) k_esdf_query(MapDev M, int s, const float* __restrict__ esdf, float gamma, float max_dist, float vs, float unknown,
@@ -27,58 +18,22 @@ __global__ void __launch_bounds__(256) k_esdf_query(MapDev M, int s, const float
 {
     const long long q = (long long)blockIdx.x * 256 + threadIdx.x;
     if (q >= n) return;
-    // an update that stopped early (tsl_esdf.hip esdf_retire: the round after the last one still had work listed, or a raise did not settle)
-    const int flag = (ctr && (ctr[2 + rounds % 3] != 0 || ctr[8] != 0)) ? EQ_SHORT : 0;
+    const int flag = esdf_short_flag(ctr, rounds);
     const float x = xyz[q * 3], y = xyz[q * 3 + 1], z = xyz[q * 3 + 2];
-    const int* __restrict__ T = M.table + (size_t)s * M.nb3;
-    float d = unknown, g0 = 0.0f, g1 = 0.0f, g2 = 0.0f;
-    int st = EQ_OUTSIDE;
-    if (MODE == 0) {
-        if (isfinite(x) && isfinite(y) && isfinite(z)) {
-            const int i = rnd_i(x / vs), j = rnd_i(y / vs), k = rnd_i(z / vs);                   // k_query_points (tsl_query.hip)
-            if (in_volume(M, i, j, k)) {
-                int l; const int p = T[brick_of(M, i, j, k, &l)];
-                const size_t v = (size_t)(p < 0 ? 0 : p) * TSL_BRK3 + l;                          // brick 0 exists: an in-bounds dummy read
-                const float t = h2f((h16)(M.tw[v] & 0xffffu)); const int o = M.obs[v]; const float e = esdf[v];
-                st = EQ_UNKNOWN;
-                if (p >= 0 && o > 0) { d = esdf_value(t, e, gamma, max_dist); st = 0; }
-            }
-        }
-    } else {
-        const float u0 = x / vs, u1 = y / vs, u2 = z / vs;
-        const int b0 = cell_floor(u0), b1 = cell_floor(u1), b2 = cell_floor(u2);
-        if (isfinite(x) && isfinite(y) && isfinite(z) && in_volume(M, b0, b1, b2) && in_volume(M, b0 + 1, b1 + 1, b2 + 1)) {
-            const float f0 = u0 - (float)b0, f1 = u1 - (float)b1, f2 = u2 - (float)b2;
-            int l000; const int bb = brick_of(M, b0, b1, b2, &l000);
-            const int li = l000 >> 8, lj = (l000 >> 4) & 15, lk = l000 & 15;
-            int P[8]; cell_bricks(M, T, bb, li, lj, lk, P);                                    // the distinct bricks only; corner c = p << 2 | q << 1 | r
-            // all 24 gathers are issued before any is used: two dependent latencies per query (table, then data)
-            uint32_t tw[8]; int ob[8]; float e[8];
-#pragma unroll
-            for (int c = 0; c < 8; ++c) {
-                const size_t v = corner_voxel(P, c, li, lj, lk);
-                tw[c] = M.tw[v]; ob[c] = M.obs[v]; e[c] = esdf[v];
-            }
-            bool known = true;
-            float V[8];
-#pragma unroll
-            for (int c = 0; c < 8; ++c) {
-                known = known && P[c] >= 0 && ob[c] > 0;
-                V[c] = esdf_value(h2f((h16)(tw[c] & 0xffffu)), e[c], gamma, max_dist);
-            }
-            st = EQ_UNKNOWN;
-            if (known) {
-                // the order of evaluation is the contract (tsl_interp.hpp, tests/esdf_query_ref.py)
-                d = tri_value(V, f0, f1, f2);
-                tri_grad(V, f0, f1, f2, &g0, &g1, &g2);
-                g0 = g0 / vs; g1 = g1 / vs; g2 = g2 / vs;
-                st = 0;
-            }
-        }
-    }
+    float d, g0, g1, g2;
+    bool nan_tsdf;                                               // not reported here: the value of such a voxel is 0 (esdf_value)
+    const int st = esdf_sample<MODE>(M, M.table + (size_t)s * M.nb3, esdf, gamma, max_dist, vs, unknown, x, y, z, &d, &g0, &g1, &g2, &nan_tsdf);
     dist[q] = d;
     if (grad) { grad[q * 3] = g0; grad[q * 3 + 1] = g1; grad[q * 3 + 2] = g2; }
     status[q] = (uint8_t)(st | flag);
+}
+
+// the refusals every read of the ESDF makes about the state of the handle (the point queries here, tsl_esdf_score_paths)
+int esdf_read_check(tsl_tsdf* m, const char* who)
+{
+    TSL_REQUIRE(m->esdf && m->esdf_query_ok, std::string(who) + ": no ESDF update since the map was created, reset or imported");
+    TSL_REQUIRE(m->esdf_submap == (m->cfg.is_global_map ? 0 : m->active), std::string(who) + ": the active submap changed since the last ESDF update");
+    return TSL_OK;
 }
 
 // the checks every form makes; *s = the submap the query reads
@@ -88,9 +43,7 @@ static int esdf_query_check(tsl_tsdf* m, int mode, const void* xyz, int64_t n, c
     TSL_REQUIRE(mode == 0 || mode == 1, std::string(who) + ": mode must be 0 (nearest voxel) or 1 (trilinear with gradient)");
     TSL_REQUIRE(!(grad && mode == 0), std::string(who) + ": the gradient needs mode 1");
     TSL_REQUIRE(n == 0 || (xyz && dist && status), std::string(who) + ": null buffer");
-    TSL_REQUIRE(m->esdf && m->esdf_query_ok, std::string(who) + ": no ESDF update since the map was created, reset or imported");
-    TSL_REQUIRE(m->esdf_submap == (m->cfg.is_global_map ? 0 : m->active), std::string(who) + ": the active submap changed since the last ESDF update");
-    return TSL_OK;
+    return esdf_read_check(m, who);
 }
 
 // launched on the handle's stream, behind the latest update (its relaxation rounds may run on another stream: esdf_overlap)

@@ -218,6 +218,7 @@ struct StageCopy { const uint4* src[2 * TSL_NB]; uint4* dst[2 * TSL_NB]; int n16
 
 int fuse_submaps_sequential(tsl_tsdf* g, tsl_tsdf* sub, const float* pose_dev, int nsrc);      // tsl_sequential.hip
 int esdf_finish(tsl_tsdf* m);            // tsl_esdf.hip: wait for the ESDF updates in flight (repairing one that stopped early)
+int esdf_read_check(tsl_tsdf* m, const char* who);      // tsl_esdf_query.hip: the refusals every read of the ESDF makes about the state of the handle
 void esdf_release(tsl_tsdf* m);
 struct FrontierState;                    // tsl_frontier.hip: scratch and result of the frontier extraction
 void frontier_release(tsl_tsdf* m);

@@ -221,6 +221,11 @@ def frontier_cluster_geometry(clusters, voxel_scale):
     return centroid.reshape(-1, 3), normal.reshape(-1, 3)
 
 
+# tsl_path_score (include/taichislam_hip.h): 40 bytes per path
+PATH_SCORE_DTYPE = np.dtype({"names": ["n_samples", "first_stop", "n_hit", "n_unknown", "n_outside", "argmin", "min_dist", "short_update", "cost"],
+                             "formats": [np.int32, np.int32, np.int32, np.int32, np.int32, np.int32, np.float32, np.int32, np.int64],
+                             "offsets": [0, 4, 8, 12, 16, 20, 24, 28, 32], "itemsize": 40})
+
 # tsl_view_gain (include/taichislam_hip.h): 64 bytes per pose at fixed offsets
 VIEW_GAIN_DTYPE = np.dtype({"names": ["n_unknown", "n_free", "vol_unknown", "vol_free", "n_hit", "n_range", "n_cut", "n_frontier"],
                             "formats": [np.int64, np.int64, np.int64, np.int64, np.int32, np.int32, np.int32, np.int32],
@@ -1273,6 +1278,81 @@ class DenseTSDF(BaseMap):
         status = np.empty(n, np.uint8)
         _lib.check(self.L.tsl_esdf_query_points(self.h, mode, float(unknown_value), _vp(x), n, _vp(dist), _vp(grad), _vp(status)))
         return dist, grad, status
+
+    def score_paths(self, waypoints, radius, margin=0.0, sub=1, lengths=None, interpolate=True, stop=False, unknown_blocks=True, outside_blocks=True,
+                    samples=False, unknown_value=float("nan"), refresh=True):
+        """Scores candidate paths against the ESDF in one launch (tsl_path_score.hip): which of these motions is free, how close
+        does each come to a surface, what does each cost.  waypoints f32 [n, K, 3] (a [K, 3] input is one path) in the frame of query_esdf; lengths
+        (integers [n], optional) gives the waypoints each path uses, 1 .. K -- the rest is never read.  Every segment is sampled at `sub` points (its
+        start and sub - 1 points between; the last waypoint closes the path), and every sample has the value and status of query_esdf there
+        (`interpolate` as there; a NaN value counts as unknown).  A sample is a hit when its distance is below `radius`; it blocks when it is a hit,
+        unknown (with unknown_blocks) or outside the volume (with outside_blocks).  Returns a dict of arrays per path: first_stop (the first blocking
+        sample, -1 for a free path), n_samples, n_hit, n_unknown, n_outside, argmin / min_dist (the closest known sample; -1 / +inf without one), cost
+        (int64: the sum of min(radius + margin - d, 1024) over the known samples closer than radius + margin, in units of 2^-20 m) and short_update
+        (0x80 when the ESDF update had stopped before converging; torch input only).  stop=True counts the samples up to first_stop only, and the GPU
+        does not evaluate the path much further.  samples=True adds sample_dist f32 [n, S_max] and sample_status u8 [n, S_max], S_max =
+        (K - 1) * sub + 1: the query's answer per counted sample, unknown_value / 0xff elsewhere.  Every field is exact and independent of the schedule.
+        numpy in -> numpy out; torch CUDA tensors in (lengths then a torch.int32 tensor) -> torch tensors, asynchronously, ordered with
+        torch.cuda.current_stream.  refresh as in query_esdf."""
+        mode = 1 if interpolate else 0
+        flags = (1 if stop else 0) | (2 if unknown_blocks else 0) | (4 if outside_blocks else 0)
+        if int(sub) < 1:
+            raise ValueError("score_paths: sub must be at least 1")
+        if refresh:
+            if not getattr(self, "_esdf_ever", False):
+                raise _lib.TslError("score_paths: call update_esdf first (refresh repeats the last update's parameters)")
+            self.update_esdf(gamma=self._esdf_gamma, max_dist=self._esdf_max_dist, wait=False)
+        if _is_device_tensor(waypoints):
+            torch = _torch()
+            w = waypoints.reshape((-1,) + tuple(waypoints.shape[-2:])).contiguous().float()
+            if w.dim() != 3 or w.shape[2] != 3:
+                raise ValueError("score_paths: waypoints must be [n, K, 3] or [K, 3]")
+            n, K = int(w.shape[0]), int(w.shape[1])
+            ln = None
+            if lengths is not None:
+                if not _is_device_tensor(lengths) or lengths.dtype != torch.int32:
+                    raise TypeError("score_paths: with torch waypoints, lengths must be a torch.int32 tensor on the same device")
+                ln = lengths.reshape(-1).contiguous()
+                if ln.shape[0] != n:
+                    raise ValueError("score_paths: one length per path")
+            smax = (K - 1) * int(sub) + 1
+            rec = torch.empty((n, 10), dtype=torch.int32, device=w.device)
+            sd = torch.empty((n, smax), dtype=torch.float32, device=w.device) if samples else None
+            ss = torch.empty((n, smax), dtype=torch.uint8, device=w.device) if samples else None
+            _lib.check(self.L.tsl_esdf_score_paths_dev(self.h, mode, float(unknown_value), w.data_ptr(), None if ln is None else ln.data_ptr(), n, K, int(sub),
+                                                       float(radius), float(margin), flags, rec.data_ptr(), None if sd is None else sd.data_ptr(),
+                                                       None if ss is None else ss.data_ptr(), torch.cuda.current_stream(w.device).cuda_stream))
+            out = {k: rec[:, i] for i, k in enumerate(PATH_SCORE_DTYPE.names[:8])}
+            out["min_dist"] = rec[:, 6].view(torch.float32)
+            out["cost"] = rec[:, 8:10].contiguous().view(torch.int64).reshape(n)
+        else:
+            w = np.asarray(waypoints, dtype=np.float32)
+            if w.ndim == 2:
+                w = w[None]
+            if w.ndim != 3 or w.shape[2] != 3:
+                raise ValueError("score_paths: waypoints must be [n, K, 3] or [K, 3]")
+            w = np.ascontiguousarray(w)
+            n, K = w.shape[0], w.shape[1]
+            ln = None
+            if lengths is not None:
+                ln = np.asarray(lengths)
+                if not np.issubdtype(ln.dtype, np.integer):
+                    raise TypeError("score_paths: lengths must be integers")
+                if ln.shape != (n,):
+                    raise ValueError("score_paths: one length per path")
+                if n and (ln.min() < 1 or ln.max() > K):
+                    raise ValueError("score_paths: a length outside 1 .. K")
+                ln = np.ascontiguousarray(ln, dtype=np.int32)
+            smax = (K - 1) * int(sub) + 1
+            rec = np.zeros(n, PATH_SCORE_DTYPE)
+            sd = np.empty((n, smax), np.float32) if samples else None
+            ss = np.empty((n, smax), np.uint8) if samples else None
+            _lib.check(self.L.tsl_esdf_score_paths(self.h, mode, float(unknown_value), _vp(w), _vp(ln), n, K, int(sub), float(radius), float(margin), flags,
+                                                   _vp(rec), _vp(sd), _vp(ss)))
+            out = {k: rec[k].copy() for k in PATH_SCORE_DTYPE.names}
+        if samples:
+            out["sample_dist"], out["sample_status"] = sd, ss
+        return out
 
     def export_esdf_torch(self):
         """(indices int16[n,3], esdf f32[n]) as torch tensors on the device: zero-copy views of the map's staging buffer, valid until the
