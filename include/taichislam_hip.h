@@ -207,6 +207,29 @@ int  tsl_mesh_read(tsl_tsdf* m, float* verts, float* normals, float* colors, int
 /* mesh_vertices / mesh_normals / mesh_colors (marching_cube_mesher.py:16-22) as DEVICE pointers, f32 [3 * max_triangles][3] (colours NULL
  * for untextured maps), + num_facelets of the last generate: taichislam_node.py:342 without the host copy */
 int  tsl_mesh_buffers_dev(tsl_tsdf* m, void** verts_dev, void** normals_dev, void** colors_dev, int32_t* n_tri);
+/* ---- indexed mesh: the mesh of tsl_mesh_generate(step 1) with welded vertices, in a canonical order (DESIGN.md "Indexed marching-cubes mesh") ----
+ * The same cells, validity rule (own voxel observed and < surface_thres, all eight corners observed), case table, sign (value < 0) and eps snap as the
+ * soup; the soup's buffers and tsl_mesh_generate are not touched.  With u = (i + N/2, j + N/2, k + Nz/2) a voxel's unsigned coordinates, its brick
+ * b = ((u.x >> 4) * nbx + (u.y >> 4)) * nbz + (u.z >> 4) (+ submap slot * bricks per submap) and l = (u.x & 15) << 8 | (u.y & 15) << 4 | (u.z & 15), its
+ * cell key is c = b * 4096 + l.
+ *   vertices   one row per GRID EDGE (lower-corner voxel, axis a = 0 / 1 / 2) that the case of at least one valid cell names, in ascending edge key c * 3 + a.
+ *              Welded by edge identity, never by position: two edges whose vertices coincide through the eps snap stay two rows.  The order is
+ *              brick-major and does not depend on the order in which the brick pool was filled.
+ *              position: vertexInterp walked from the lower corner (p0) to the upper one (p1), times voxel_scale -- bit for bit the soup's vertex
+ *              wherever the soup's cell walks the edge that way (table edges 2, 3, 6, 7 walk it the other way and differ by up to 2^-11 voxel);
+ *              normal: the f16 generate_normal at that position; colour (textured maps): vertexInterp_color with the same p0 / p1 and mu;
+ *              edge record: int16 (i, j, k, axis), the signed voxel index of the lower corner.
+ *   triangles  int32[3] vertex rows, in ascending cell key, then in the order of the case's table row; the corners keep the table's order.  As many as the soup has.
+ * tsl_mesh_generate_indexed issues the queued frames first, runs on the handle's stream and waits for the counts.  n_vertices / n_triangles are the TRUE
+ * counts; every row below its capacity (max_vertices, max_triangles: both > 0) holds exactly the canonical row, nothing is written beyond it -- a stored
+ * triangle may then name a vertex row that is not stored.  The buffers live on the handle and only grow. */
+int  tsl_mesh_generate_indexed(tsl_tsdf* m, float surface_thres, int64_t max_vertices, int64_t max_triangles, int64_t* n_vertices, int64_t* n_triangles);
+/* the first n_vertices rows of verts f32[.][3], normals f32[.][3], colors f32[.][3] (left alone for an untextured map), edges int16[.][4] and the first n_triangles
+ * rows of indices int32[.][3] of the last tsl_mesh_generate_indexed; any pointer may be NULL.  Refused: more rows than that call stored (min(count, capacity)). */
+int  tsl_mesh_read_indexed(tsl_tsdf* m, float* verts, float* normals, float* colors, int16_t* edges, int32_t* indices, int64_t n_vertices, int64_t n_triangles);
+/* the same five arrays as DEVICE pointers (colours NULL for an untextured map) and the true counts of the last tsl_mesh_generate_indexed; the pointers
+ * change when a later call asks for a larger capacity.  Any pointer may be NULL. */
+int  tsl_mesh_indexed_dev(tsl_tsdf* m, void** verts_dev, void** normals_dev, void** colors_dev, void** edges_dev, void** indices_dev, int64_t* n_vertices, int64_t* n_triangles);
 
 /* ---- coordinates that are not finite ----------------------------------------------------------------------------------------------
  * A coordinate that is not finite (NaN, +-inf), or whose cell index rnd(x / voxel) does not fit an int, lies OUTSIDE every map.  The entry points that

@@ -222,6 +222,9 @@ SIGNATURES = {
     "tsl_mesh_generate": (C.c_int, [vp, C.c_int, f32, i64, pi32]),
     "tsl_mesh_read": (C.c_int, [vp, vp, vp, vp, i64]),
     "tsl_mesh_buffers_dev": (C.c_int, [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), pi32]),
+    "tsl_mesh_generate_indexed": (C.c_int, [vp, f32, i64, i64, pi64, pi64]),
+    "tsl_mesh_read_indexed": (C.c_int, [vp, vp, vp, vp, vp, vp, i64, i64]),
+    "tsl_mesh_indexed_dev": (C.c_int, [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), pi64, pi64]),
     "tsl_tsdf_query_points": (C.c_int, [vp, C.c_int, C.c_int, vp, i64, vp]),
     "tsl_tsdf_query_raycast": (C.c_int, [vp, vp, vp, f32, i64, vp, vp, vp]),
     "tsl_tsdf_query_points_dev": (C.c_int, [vp, C.c_int, C.c_int, vp, i64, vp, vp]),

@@ -224,6 +224,8 @@ struct FrontierState;                    // tsl_frontier.hip: scratch and result
 void frontier_release(tsl_tsdf* m);
 struct GainState;                        // tsl_view_gain.hip: the pinned staging of a call's pose table
 void gain_release(tsl_tsdf* m);
+struct MeshIdxState;                     // tsl_mesh_indexed.hip: scratch and buffers of the indexed mesh (allocated by the first call)
+void mesh_indexed_release(tsl_tsdf* m);
 }  // namespace tsl
 
 #define TSL_ESDF_SLOTS 4
@@ -291,6 +293,7 @@ struct tsl_tsdf {
     unsigned long long *seq_keys[2], *seq_vals[2], *seq_ctr; void* seq_temp; size_t seq_temp_bytes; long long seq_cap;
     tsl::FrontierState* frontier;        // tsl_frontier.hip (allocated by the first extraction)
     tsl::GainState* gain;                // tsl_view_gain.hip (allocated by the first call)
+    tsl::MeshIdxState* mesh_idx;         // tsl_mesh_indexed.hip (allocated by the first call)
     int variant, split, phases, wg, spt, ncu, chunks, unit_max, unit_half, unit_floor, bgrid, ugrid, pgrid, split_launch, adaptive, ramp, ramp_batches, ramp_size; bool clean; uint64_t batch_gen;
     int64_t bytes;
     void* seqv_sum[TSL_NBATCH]; int* seqv_log;      // TSL_SEQ_VERIFY (developer aid, tsl_sequential.hip): per-item checksums, mismatch log
