@@ -67,6 +67,7 @@ enum { TSL_K_VOXELIZE = 0, TSL_K_SORT = 1, TSL_K_RAYS = 2, TSL_K_INTEGRATE = 3, 
        TSL_K_MESH = 5, TSL_K_SEGMENTS = 6, TSL_K_BIN = 7, TSL_K_ESDF = 8, TSL_K_FUSE = 9, TSL_K_REGISTER = 10,
        TSL_K_REGISTER_SCORE = 11, TSL_K_FRONTIER_MARK = 12, TSL_K_FRONTIER_LABEL = 13, TSL_K_FRONTIER_JOIN = 14, TSL_K_FRONTIER_SUM = 15,
        TSL_K_FRONTIER_EMIT = 16, TSL_K_VIEW_GAIN = 17, TSL_K_ALIGN = 18, TSL_K_ALIGN_POINTS = 19, TSL_K_PATH_SCORE = 20,
+       TSL_K_NAV_PROJECT = 21, TSL_K_NAV_EDT = 22, TSL_K_NAV_EDT_ROWS = 23,
        TSL_K_COUNT };
 
 const char* tsl_version(void);
@@ -635,6 +636,45 @@ int  tsl_tsdf_view_gain(tsl_tsdf* m, const double* R /* n x 9 */, const double* 
                         int32_t* ray_unknown, uint8_t* ray_status);
 int  tsl_tsdf_view_gain_dev(tsl_tsdf* m, const double* R, const double* T, int32_t n, const tsl_gain_cfg* cfg, void* out_dev, void* ray_unknown_dev,
                             void* ray_status_dev, void* user_stream);
+
+/* ---- navigation grids (tsl_nav_grid.hip): height bands of the TSDF projected into 2-D grids -- per band and (x, y) column a class, the squared planar
+ * distance to the nearest obstacle column and a cost: the nav_msgs/OccupancyGrid and costmap layer a ground robot, or a drone that plans in altitude
+ * layers, consumes.  The reference has no such pass.  Everything is integer except the one f32 comparison of the voxel
+ * classes: the result depends on no schedule and tests/nav_grid_ref.py restates it bit for bit.  The pass reads one submap slot, the one of
+ * tsl_tsdf_query_points (the active submap; submap 0 on a global map), and writes nothing to the map or the ESDF.
+ *   Voxel classes: those of tsl_tsdf_frontier_extract -- UNKNOWN: the brick is absent or the observed count is <= 0; OCCUPIED: observed and the f16 TSDF,
+ *     widened to f32, is < thres; FREE: every other observed voxel; thres = free_thres, 0 = the map's surface threshold.  ONE difference: an observed
+ *     voxel whose TSDF is a NaN (it can only come in through tsl_tsdf_import_sparse) is UNKNOWN here, while the frontier pass calls it FREE: a navigation
+ *     grid must not call such a voxel free.
+ *   Bands: n_bands = B in 1 .. 16; band b is the voxel layers k_min[b] <= k <= k_max[b] (signed voxel indices, both ends inclusive), inside
+ *     -Nz/2 .. Nz/2 - 1, k_min <= k_max.  Bands may overlap or be equal; the map is read once however many there are.
+ *   Column counts: per band and column (i, j) of the N x N footprint, n_occ, n_free, n_unknown over the band's layers (they sum to its height), and
+ *     lo / hi, the lowest / highest OCCUPIED layer k of the band (32767 / -32768 when there is none).
+ *   Cell class (u8), tested in this order: TSL_NAV_OCCUPIED (1) when n_occ >= min_occ; TSL_NAV_FREE (0) when n_free >= min_free and (max_unknown < 0 or
+ *     n_unknown <= max_unknown); TSL_NAV_UNKNOWN (2) otherwise.  min_occ / min_free 0 = 1.
+ *   Distance: with ui = i + N/2, uj = j + N/2, the obstacles of a band are its OCCUPIED cells; with flags bit 0 its UNKNOWN cells too; with flags bit 1
+ *     every position just outside the grid (ui or uj equal to -1 or N: the wall of the volume).  radius = R in 0 .. 254 voxels.  d2 (uint16) is the exact
+ *     squared Euclidean distance in voxels to the nearest obstacle when that is <= R * R, and R * R + 1 otherwise; an obstacle cell has d2 = 0.
+ *   Cost: lut is a u8 [R * R + 2] table of the caller's (the inflation formula lives in the table, not in the kernel); cost = cost_unknown for an
+ *     UNKNOWN cell, else lut[d2].
+ *   Layout: every plane is [B][N][N], indexed [b][ui][uj]; counts is uint16 [B][N][N][3] = { n_occ, n_free, n_unknown }, span int16 [B][N][N][2] = { lo, hi }.
+ * Every output is nullable on its own (a plane that is not asked for is not computed where that is separable: without d2 and cost the distance
+ * transform does not run); cost and lut come together or not at all.  tsl_tsdf_nav_grid issues the queued frames, runs on the handle's stream behind
+ * them, waits and copies back.  tsl_tsdf_nav_grid_dev takes device pointers, is ASYNCHRONOUS and ordered with `user_stream` like
+ * tsl_tsdf_render_view_dev.  Scratch on the handle grows as needed.  With profiling on, tsl_tsdf_prof_query returns the time of the stages:
+ * TSL_K_NAV_PROJECT (the column reduction), TSL_K_NAV_EDT_ROWS (the distance pass along j) and TSL_K_NAV_EDT (the pass along i with the cost lookup).
+ * TSL_ERR_ARG, before anything is launched or written (the text names the entry point): a null handle or cfg; every output null; n_bands outside
+ * 1 .. 16; a band outside the volume or with k_min > k_max; a free_thres that is not finite; a negative min_occ or min_free; radius outside 0 .. 254;
+ * flag bits other than 0 and 1; cost without lut or lut without cost; N * N * n_bands >= 2^31.  A refused call leaves the handle usable. */
+#define TSL_NAV_FREE 0
+#define TSL_NAV_OCCUPIED 1
+#define TSL_NAV_UNKNOWN 2
+typedef struct { int32_t n_bands, k_min[16], k_max[16]; float free_thres; int32_t min_occ, min_free, max_unknown, radius, flags;
+                 uint8_t cost_unknown, reserved_[3]; } tsl_nav_cfg;
+int  tsl_tsdf_nav_grid(tsl_tsdf* m, const tsl_nav_cfg* cfg, const uint8_t* lut, uint8_t* cls, uint16_t* d2, uint8_t* cost,
+                       uint16_t* counts /* [B][N][N][3] */, int16_t* span /* [B][N][N][2] */);
+int  tsl_tsdf_nav_grid_dev(tsl_tsdf* m, const tsl_nav_cfg* cfg, const void* lut_dev, void* cls_dev, void* d2_dev, void* cost_dev, void* counts_dev,
+                           void* span_dev, void* user_stream);
 
 /* backend knobs for A/B-ing kernel variants: name in
      "variant"  0|1: one global int64 atomic pair per ray step, 2 (default): brick-binned LDS accumulation

@@ -9,11 +9,12 @@ TSL_OK = 0
 K_VOXELIZE, K_SORT, K_RAYS, K_INTEGRATE, K_FINALIZE, K_MESH, K_SEGMENTS, K_BIN, K_ESDF, K_FUSE, K_REGISTER, K_REGISTER_SCORE = range(12)
 K_FRONTIER_MARK, K_FRONTIER_LABEL, K_FRONTIER_JOIN, K_FRONTIER_SUM, K_FRONTIER_EMIT = range(12, 17)
 K_VIEW_GAIN, K_ALIGN, K_ALIGN_POINTS, K_PATH_SCORE = 17, 18, 19, 20
+K_NAV_PROJECT, K_NAV_EDT, K_NAV_EDT_ROWS = 21, 22, 23
 KERNEL_NAMES = {K_VOXELIZE: "voxelize", K_SORT: "sort", K_RAYS: "build_rays", K_INTEGRATE: "integrate",
                 K_FINALIZE: "finalize", K_MESH: "marching_cubes", K_SEGMENTS: "segments", K_BIN: "bin", K_ESDF: "esdf", K_FUSE: "fuse", K_REGISTER: "register",
                 K_REGISTER_SCORE: "register_score", K_FRONTIER_MARK: "frontier_mark", K_FRONTIER_LABEL: "frontier_label", K_FRONTIER_JOIN: "frontier_join",
                 K_FRONTIER_SUM: "frontier_sum", K_FRONTIER_EMIT: "frontier_emit", K_VIEW_GAIN: "view_gain", K_ALIGN: "align", K_ALIGN_POINTS: "align_points",
-                K_PATH_SCORE: "path_score"}
+                K_PATH_SCORE: "path_score", K_NAV_PROJECT: "nav_project", K_NAV_EDT: "nav_edt", K_NAV_EDT_ROWS: "nav_edt_rows"}
 
 
 class TsdfCfg(C.Structure):
@@ -155,6 +156,14 @@ class PathScore(C.Structure):
                 ("argmin", C.c_int32), ("min_dist", C.c_float), ("short_update", C.c_int32), ("cost", C.c_int64)]
 
 
+class NavCfg(C.Structure):
+    """tsl_nav_cfg (tsl_tsdf_nav_grid): n_bands bands of voxel layers k_min[b] .. k_max[b]; free_thres 0 = the map's surface threshold, min_occ / min_free
+    0 = 1, max_unknown < 0 = no limit, radius in voxels, flags bit 0 = unknown cells are obstacles, bit 1 = so is the wall of the volume"""
+    _fields_ = [("n_bands", C.c_int32), ("k_min", C.c_int32 * 16), ("k_max", C.c_int32 * 16), ("free_thres", C.c_float), ("min_occ", C.c_int32),
+                ("min_free", C.c_int32), ("max_unknown", C.c_int32), ("radius", C.c_int32), ("flags", C.c_int32), ("cost_unknown", C.c_uint8),
+                ("reserved_", C.c_uint8 * 3)]
+
+
 class TslError(RuntimeError):
     pass
 
@@ -264,6 +273,8 @@ SIGNATURES = {
     "tsl_tsdf_frontier_dev": (C.c_int, [vp, C.POINTER(FrontierCfg), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), pi32, pi32, vp]),
     "tsl_tsdf_view_gain": (C.c_int, [vp, dp, dp, i32, C.POINTER(GainCfg), vp, vp, vp]),
     "tsl_tsdf_view_gain_dev": (C.c_int, [vp, dp, dp, i32, C.POINTER(GainCfg), vp, vp, vp, vp]),
+    "tsl_tsdf_nav_grid": (C.c_int, [vp, C.POINTER(NavCfg), vp, vp, vp, vp, vp, vp]),
+    "tsl_tsdf_nav_grid_dev": (C.c_int, [vp, C.POINTER(NavCfg), vp, vp, vp, vp, vp, vp, vp]),
     "tsl_tsdf_set_option": (C.c_int, [vp, C.c_char_p, C.c_int]),
     "tsl_tsdf_get_option": (C.c_int, [vp, C.c_char_p, C.POINTER(C.c_int)]),
     "tsl_tsdf_prof_enable": (C.c_int, [vp, C.c_int]),

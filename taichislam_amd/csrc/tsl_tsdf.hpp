@@ -226,6 +226,8 @@ struct GainState;                        // tsl_view_gain.hip: the pinned stagin
 void gain_release(tsl_tsdf* m);
 struct MeshIdxState;                     // tsl_mesh_indexed.hip: scratch and buffers of the indexed mesh (allocated by the first call)
 void mesh_indexed_release(tsl_tsdf* m);
+struct NavState;                         // tsl_nav_grid.hip: scratch and host staging of the navigation grids (allocated by the first call)
+void nav_release(tsl_tsdf* m);
 }  // namespace tsl
 
 #define TSL_ESDF_SLOTS 4
@@ -298,6 +300,7 @@ struct tsl_tsdf {
     int64_t bytes;
     void* seqv_sum[TSL_NBATCH]; int* seqv_log;      // TSL_SEQ_VERIFY (developer aid, tsl_sequential.hip): per-item checksums, mismatch log
     uint32_t shape_hash; int dry_launches;      // developer statistics: FNV hash over the sizes of the batches issued so far; batches issued into a dry pipeline
+    tsl::NavState* nav;                  // tsl_nav_grid.hip (allocated by the first call)
 };
 
 namespace tsl {

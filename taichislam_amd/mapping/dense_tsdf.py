@@ -221,6 +221,8 @@ def frontier_cluster_geometry(clusters, voxel_scale):
     return centroid.reshape(-1, 3), normal.reshape(-1, 3)
 
 
+NAV_FREE, NAV_OCCUPIED, NAV_UNKNOWN = 0, 1, 2          # cell classes of DenseTSDF.nav_grid (TSL_NAV_* of include/taichislam_hip.h)
+
 # tsl_path_score (include/taichislam_hip.h): 40 bytes per path
 PATH_SCORE_DTYPE = np.dtype({"names": ["n_samples", "first_stop", "n_hit", "n_unknown", "n_outside", "argmin", "min_dist", "short_update", "cost"],
                              "formats": [np.int32, np.int32, np.int32, np.int32, np.int32, np.int32, np.float32, np.int32, np.int64],
@@ -991,6 +993,99 @@ class DenseTSDF(BaseMap):
             out = {"indices": idx, "xyz": idx.astype(np.float32) * vs, "mask": mask, "cluster": cl}
         out["clusters"] = clusters
         out["centroid"], out["normal"] = frontier_cluster_geometry(clusters, float(self.voxel_scale))
+        return out
+
+    # ---- navigation grids (tsl_nav_grid.hip, DESIGN.md section 4.15) ---------------------------------------------------------
+    def _nav_bands(self, bands, z_range):
+        """[(k_min, k_max)] of nav_grid: `bands` as given (voxel layers; the library checks them), else z_range -- one (z0, z1) in metres or a list of them --
+        turned into layers the way extract_frontiers does and clamped to the volume, else the whole height"""
+        if bands is not None and z_range is not None:
+            raise ValueError("nav_grid: give bands or z_range, not both")
+        lo, hi = -(self.Nz // 2), self.Nz // 2 - 1
+        if bands is not None:
+            out = [(int(a), int(b)) for a, b in bands]
+        elif z_range is None:
+            out = [(lo, hi)]
+        else:
+            zr = list(z_range)
+            if len(zr) == 2 and not hasattr(zr[0], "__len__"):
+                zr = [zr]
+            out = []
+            for z in zr:
+                z0, z1 = float(z[0]), float(z[1])
+                if not (math.isfinite(z0) and math.isfinite(z1)):
+                    raise ValueError("nav_grid: z_range is not finite")
+                k0 = max(lo, math.ceil(z0 / float(self.voxel_scale)))
+                k1 = min(hi, math.floor(z1 / float(self.voxel_scale)))
+                if k0 > k1:
+                    raise ValueError("nav_grid: a z_range holds no voxel layer of the volume")
+                out.append((k0, k1))
+        if not 1 <= len(out) <= 16:
+            raise ValueError("nav_grid: 1 .. 16 bands")
+        return out
+
+    def nav_grid(self, bands=None, z_range=None, radius=1.0, free_thres=None, min_occ=1, min_free=1, max_unknown=None, unknown_is_obstacle=False,
+                 wall_is_obstacle=False, lut=None, cost_unknown=255, counts=False, span=False, device=False):
+        """Height bands of the submap the point queries read (the active one; submap 0 on a global map) as 2-D navigation grids: what a 2-D planner or a
+        costmap layer consumes.  bands: [(k_min, k_max)] voxel layers, both ends inclusive, or z_range: (z0, z1) in metres or a list of them (the layers
+        with z0 <= k * voxel <= z1, clamped to the volume; an empty band raises); neither = the whole height; at most 16.  Per band and (x, y) column the
+        voxels are classed as extract_frontiers does (free_thres as there; an observed NaN counts as unknown) and counted; the cell is occupied
+        (NAV_OCCUPIED = 1) when at least min_occ are occupied, else free (NAV_FREE = 0) when at least min_free are free and at most max_unknown unknown
+        (None = no limit), else unknown (NAV_UNKNOWN = 2).  d2 is the exact squared distance in voxels to the nearest obstacle cell -- occupied cells,
+        with unknown_is_obstacle the unknown ones too, with wall_is_obstacle the positions just outside the grid -- up to `radius` (metres, rounded to
+        voxels, at most 254 voxels): R * R + 1 beyond it.  lut: a u8 table of R * R + 2 costs (utils.inflation_lut); cost = cost_unknown for an unknown
+        cell, else lut[d2].  Returns a dict: `cls` u8 [B, N, N], `d2` uint16 [B, N, N], with lut `cost` u8 [B, N, N], with counts=True `counts` uint16
+        [B, N, N, 3] (occupied, free, unknown voxels), with span=True `span` int16 [B, N, N, 2] (lowest / highest occupied layer; 32767 / -32768 when
+        none) -- every plane indexed [b][i + N / 2][j + N / 2] -- and `voxel`, `origin_xy` = (-(N / 2) - 0.5) * voxel (the corner of cell 0, 0),
+        `bands`, `radius_vox`.  device=True returns the planes as torch tensors on the map's device, asynchronously, ordered with
+        torch.cuda.current_stream (tsl_tsdf_nav_grid_dev); otherwise numpy arrays."""
+        bl = self._nav_bands(bands, z_range)
+        radius = float(radius)
+        if not math.isfinite(radius) or radius < 0.0:
+            raise ValueError("nav_grid: radius must be finite and not negative")
+        R = int(round(radius / float(self.voxel_scale)))
+        if free_thres is not None and not float(free_thres) > 0.0:
+            raise ValueError("nav_grid: free_thres must be positive")
+        cfg = _lib.NavCfg()
+        cfg.n_bands = len(bl)
+        for b, (k0, k1) in enumerate(bl):
+            cfg.k_min[b], cfg.k_max[b] = k0, k1
+        cfg.free_thres = 0.0 if free_thres is None else float(free_thres)
+        cfg.min_occ, cfg.min_free = int(min_occ), int(min_free)
+        cfg.max_unknown = -1 if max_unknown is None else max(0, int(max_unknown))
+        cfg.radius = R
+        cfg.flags = (1 if unknown_is_obstacle else 0) | (2 if wall_is_obstacle else 0)
+        cfg.cost_unknown = int(cost_unknown) & 0xff
+        if lut is not None:
+            lut = np.ascontiguousarray(np.asarray(lut, dtype=np.uint8).reshape(-1))
+            if lut.size != R * R + 2:
+                raise ValueError(f"nav_grid: lut must hold R * R + 2 = {R * R + 2} entries, not {lut.size}")
+        B, N = len(bl), self.N
+        out = {"voxel": float(self.voxel_scale), "origin_xy": (-(N // 2) - 0.5) * float(self.voxel_scale), "bands": bl, "radius_vox": R}
+        if device:
+            torch = _torch()
+            dev = torch.device(f"cuda:{self.device}")
+            u16 = _DEPTH_DTYPES(torch)[1]
+            cls = torch.empty((B, N, N), dtype=torch.uint8, device=dev)
+            d2 = torch.empty((B, N, N), dtype=u16, device=dev)
+            cost = torch.empty((B, N, N), dtype=torch.uint8, device=dev) if lut is not None else None
+            cnt = torch.empty((B, N, N, 3), dtype=u16, device=dev) if counts else None
+            sp = torch.empty((B, N, N, 2), dtype=torch.int16, device=dev) if span else None
+            lut_d = torch.from_numpy(lut).to(dev) if lut is not None else None
+            ptr = lambda t: None if t is None else t.data_ptr()
+            _lib.check(self.L.tsl_tsdf_nav_grid_dev(self.h, C.byref(cfg), ptr(lut_d), ptr(cls), ptr(d2), ptr(cost), ptr(cnt), ptr(sp),
+                                                    torch.cuda.current_stream(dev).cuda_stream))
+        else:
+            cls = np.empty((B, N, N), np.uint8)
+            d2 = np.empty((B, N, N), np.uint16)
+            cost = np.empty((B, N, N), np.uint8) if lut is not None else None
+            cnt = np.empty((B, N, N, 3), np.uint16) if counts else None
+            sp = np.empty((B, N, N, 2), np.int16) if span else None
+            _lib.check(self.L.tsl_tsdf_nav_grid(self.h, C.byref(cfg), _vp(lut), _vp(cls), _vp(d2), _vp(cost), _vp(cnt), _vp(sp)))
+        out["cls"], out["d2"] = cls, d2
+        for k, v in (("cost", cost), ("counts", cnt), ("span", sp)):
+            if v is not None:
+                out[k] = v
         return out
 
     # ---- frame-to-model alignment (tsl_align.hip, DESIGN.md section 4.8) ---------------------------------------------------

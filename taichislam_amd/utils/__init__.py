@@ -1,0 +1,1 @@
+from .nav import inflation_lut  # noqa: F401

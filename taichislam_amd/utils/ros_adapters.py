@@ -30,3 +30,29 @@ def to_ros(payload, frame_id="world", stamp=None):
     return sensor_msgs.PointCloud2(header=header, height=payload["height"], width=payload["width"], is_dense=payload["is_dense"],
                                    is_bigendian=payload["is_bigendian"], fields=fields, point_step=payload["point_step"],
                                    row_step=payload["row_step"], data=payload["data"])
+
+
+def occupancy_grid_fields(grid, band, cost=False):
+    """The fields of a nav_msgs/OccupancyGrid for band `band` of a DenseTSDF.nav_grid result, as plain Python values: resolution (metres per cell), width
+    (cells along x), height (cells along y), origin (x, y, z of the lower corner of cell (0, 0); z = the band's lowest layer) and data, int8 [height *
+    width] with x fastest -- data[y * width + x] -- holding -1 for an unknown cell, 100 for an occupied and 0 for a free one.  With cost=True a known
+    cell holds its cost scaled to 0 .. 100, min(100, (cost * 100 + 127) // 254); the grid must then carry a cost plane (nav_grid(lut=...)).  The planes
+    of nav_grid are indexed [x][y], the message's data [y][x]: this is the transpose."""
+    def host(a):
+        return np.asarray(a.cpu().numpy() if hasattr(a, "cpu") else a)
+    b = int(band)
+    cls = host(grid["cls"])
+    if not 0 <= b < cls.shape[0]:
+        raise ValueError(f"occupancy_grid_fields: band {b} of {cls.shape[0]}")
+    c = cls[b]
+    if cost:
+        if "cost" not in grid:
+            raise ValueError("occupancy_grid_fields: cost=True needs the cost plane (nav_grid(lut=...))")
+        v = np.minimum(100, (host(grid["cost"])[b].astype(np.int32) * 100 + 127) // 254)
+    else:
+        v = np.where(c == 1, 100, 0)
+    data = np.where(c == 2, -1, v).astype(np.int8).T              # [y][x]
+    vs = float(grid["voxel"])
+    o = float(grid["origin_xy"])
+    return {"resolution": vs, "width": int(c.shape[0]), "height": int(c.shape[1]), "origin": (o, o, float(grid["bands"][b][0]) * vs),
+            "data": np.ascontiguousarray(data).reshape(-1)}
