@@ -68,6 +68,7 @@ enum { TSL_K_VOXELIZE = 0, TSL_K_SORT = 1, TSL_K_RAYS = 2, TSL_K_INTEGRATE = 3, 
        TSL_K_REGISTER_SCORE = 11, TSL_K_FRONTIER_MARK = 12, TSL_K_FRONTIER_LABEL = 13, TSL_K_FRONTIER_JOIN = 14, TSL_K_FRONTIER_SUM = 15,
        TSL_K_FRONTIER_EMIT = 16, TSL_K_VIEW_GAIN = 17, TSL_K_ALIGN = 18, TSL_K_ALIGN_POINTS = 19, TSL_K_PATH_SCORE = 20,
        TSL_K_NAV_PROJECT = 21, TSL_K_NAV_EDT = 22, TSL_K_NAV_EDT_ROWS = 23,
+       TSL_K_NAV_FIELD_SEED = 24, TSL_K_NAV_FIELD_ROUND = 25, TSL_K_NAV_FIELD_PARENT = 26, TSL_K_NAV_FIELD_PATHS = 27,
        TSL_K_COUNT };
 
 const char* tsl_version(void);
@@ -675,6 +676,59 @@ int  tsl_tsdf_nav_grid(tsl_tsdf* m, const tsl_nav_cfg* cfg, const uint8_t* lut, 
                        uint16_t* counts /* [B][N][N][3] */, int16_t* span /* [B][N][N][2] */);
 int  tsl_tsdf_nav_grid_dev(tsl_tsdf* m, const tsl_nav_cfg* cfg, const void* lut_dev, void* cls_dev, void* d2_dev, void* cost_dev, void* counts_dev,
                            void* span_dev, void* user_stream);
+
+/* ---- cost-to-go fields and paths over 2-D cost planes (tsl_nav_field.hip): how expensive it is to get from every cell to the
+ * nearest goal, along which cells, and which cells reach no goal -- what a 2-D planner or an exploration loop asks once it holds a cost plane.  The
+ * planes are the CALLER'S: u8 [B][H][W], 1 <= H, W <= 4096, 1 <= B <= 16, usually the `cost` output of tsl_tsdf_nav_grid, possibly cropped or with
+ * obstacles painted in.  The handle supplies only the device, the stream and scratch (allocated by the first call); no map is read.  Everything is
+ * integer and the answer is the one minimum of a sum of positive integers: it depends on no schedule, and tests/nav_field_ref.py restates it bit for bit.
+ *   Traversable: cost < lethal; lethal in 1 .. 255 (253 keeps nav_grid's cost_unknown = 255 and an inflation table's 253 / 254 as walls).
+ *   Moves: connectivity 4 or 8.  Direction codes 0 .. 7 are (di, dj) = (1,0) (1,1) (0,1) (-1,1) (-1,0) (-1,-1) (0,-1) (1,-1), i the row and j the column;
+ *     odd codes exist only with connectivity 8, and a diagonal move is allowed only when both cells it passes between are traversable (no corner
+ *     cutting).  Step length s = 5 for an axis move, 7 for a diagonal one.
+ *   Seeds: int32 [S][4] = { plane, row, col, value }, 0 <= S <= 65536, value read as uint32 (2^32 - 1 counts as 2^32 - 2).  A seed outside the planes or
+ *     on a cell that is not traversable is ignored and counted in n_bad_seeds; of several seeds on one cell the least value counts; planes are
+ *     independent problems.  S = 0 is no error: everything is unreached.
+ *   field (uint32 [B][H][W]): the minimum over all move sequences x = c0, c1, .., cm = a seed cell through traversable cells of
+ *     value(seed) + sum over t < m of s(c_t -> c_t+1) * (neutral + cost[c_t]), clipped to 2^32 - 2; TSL_NAV_UNREACHED = 2^32 - 1 where no seed is
+ *     reached (walls included).  neutral in 1 .. 255.
+ *   parent (u8 [B][H][W], nullable; a pass of its own after the rounds): 255 for an unreached cell; 8 for a cell whose field equals a seed value placed
+ *     on it; otherwise the lowest direction code d whose move is allowed and whose neighbour n satisfies
+ *     min(field[n] + s_d * (neutral + cost[x]), 2^32 - 2) == field[x].  (Only a field that did not converge has reached cells that no neighbour
+ *     explains; they get 255.)
+ *   Rounds: one round is one launch; a 32 x 32 tile that is marked active relaxes in LDS against a one-cell halo, writes its own cells back and marks
+ *     the neighbours whose halo changed for the next round.  No workgroup waits for another and every loop in a kernel has a bound known at launch.
+ *     The host ends the rounds: every check_every rounds (0 = 8) it reads 4 bytes, the marks the last round made, and stops after a round that
+ *     marked nothing or at max_rounds (0 = 4 * tiles of a plane + 64).  Not converged is converged = 0 WITH TSL_OK -- the field then holds upper
+ *     bounds, each the cost of a real move sequence -- and never a wait.  With rounds_fixed > 0 exactly that many rounds are enqueued and nothing is
+ *     read; rounds_fixed = the `rounds` of an earlier call on the same input ends on converged = 1 (field and parent depend on no schedule; the
+ *     round count can: a halo read that meets a neighbour's write-back saves work, so where not all tiles of a round run at once read converged).
+ *   Statistics: converged; rounds = the last round that visited a tile, counted from 1; tile_visits; n_bad_seeds.
+ * tsl_tsdf_nav_field takes host pointers, issues the queued frames, runs on the handle's stream, waits and copies back.  tsl_tsdf_nav_field_dev takes
+ * device pointers (stats_dev: a tsl_nav_field_stats in device memory, nullable) and is ordered with `user_stream` like tsl_tsdf_nav_grid_dev: with
+ * rounds_fixed > 0 it is ASYNCHRONOUS; with rounds_fixed = 0 it SYNCHRONISES the handle's stream at each check, and so waits for the work of
+ * `user_stream` queued before it.
+ *   Paths (tsl_tsdf_nav_field_paths / _dev; cfg gives B, H, W): starts int32 [P][3] = { plane, row, col }, 0 <= P <= 2^20, P * L <= 2^28.  One lane per
+ *     start follows `parent` for at most L = max_len cells.  cells int16 [P][L][2] = (row, col) from the start on, rows past the end -1; length int32
+ *     [P]; status u8 [P]: 0 = ended on a seed, 1 = truncated at L, 2 = the start is unreached or not traversable (or the parents lead nowhere: a plane
+ *     that is not of this field), 3 = the start is outside; cost uint32 [P] = the field at the start (TSL_NAV_UNREACHED for status 3).  Every output
+ *     is nullable.  The _dev form is asynchronous.
+ * With profiling on, tsl_tsdf_prof_query returns the time of TSL_K_NAV_FIELD_SEED, TSL_K_NAV_FIELD_ROUND (every round of the calls), TSL_K_NAV_FIELD_PARENT
+ * and TSL_K_NAV_FIELD_PATHS.
+ * TSL_ERR_ARG, before anything is launched or written (the text names the entry point): a null handle, cfg, cost or field (paths: field or parent); B
+ * outside 1 .. 16, H or W outside 1 .. 4096, S outside 0 .. 65536; neutral or lethal outside 1 .. 255; a connectivity other than 4 and 8; seeds null
+ * while S > 0 (starts while P > 0); max_len < 1; a negative max_rounds, rounds_fixed or check_every.  A refused call leaves the handle usable. */
+#define TSL_NAV_UNREACHED 0xffffffffu
+typedef struct { int32_t B, H, W, neutral, lethal, connectivity, max_rounds, rounds_fixed, check_every, reserved_; } tsl_nav_field_cfg;
+typedef struct { int32_t converged, rounds; int64_t tile_visits; int32_t n_bad_seeds, reserved_; } tsl_nav_field_stats;
+int  tsl_tsdf_nav_field(tsl_tsdf* m, const tsl_nav_field_cfg* cfg, const uint8_t* cost, const int32_t* seeds /* [S][4] */, int32_t n_seeds, uint32_t* field,
+                        uint8_t* parent, tsl_nav_field_stats* stats);
+int  tsl_tsdf_nav_field_dev(tsl_tsdf* m, const tsl_nav_field_cfg* cfg, const void* cost_dev, const void* seeds_dev, int32_t n_seeds, void* field_dev,
+                            void* parent_dev, void* stats_dev, void* user_stream);
+int  tsl_tsdf_nav_field_paths(tsl_tsdf* m, const tsl_nav_field_cfg* cfg, const uint32_t* field, const uint8_t* parent, const int32_t* starts /* [P][3] */,
+                              int32_t n_starts, int32_t max_len, int16_t* cells /* [P][L][2] */, int32_t* length, uint8_t* status, uint32_t* cost);
+int  tsl_tsdf_nav_field_paths_dev(tsl_tsdf* m, const tsl_nav_field_cfg* cfg, const void* field_dev, const void* parent_dev, const void* starts_dev,
+                                  int32_t n_starts, int32_t max_len, void* cells_dev, void* length_dev, void* status_dev, void* cost_dev, void* user_stream);
 
 /* backend knobs for A/B-ing kernel variants: name in
      "variant"  0|1: one global int64 atomic pair per ray step, 2 (default): brick-binned LDS accumulation

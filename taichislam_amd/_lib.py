@@ -10,11 +10,14 @@ K_VOXELIZE, K_SORT, K_RAYS, K_INTEGRATE, K_FINALIZE, K_MESH, K_SEGMENTS, K_BIN, 
 K_FRONTIER_MARK, K_FRONTIER_LABEL, K_FRONTIER_JOIN, K_FRONTIER_SUM, K_FRONTIER_EMIT = range(12, 17)
 K_VIEW_GAIN, K_ALIGN, K_ALIGN_POINTS, K_PATH_SCORE = 17, 18, 19, 20
 K_NAV_PROJECT, K_NAV_EDT, K_NAV_EDT_ROWS = 21, 22, 23
+K_NAV_FIELD_SEED, K_NAV_FIELD_ROUND, K_NAV_FIELD_PARENT, K_NAV_FIELD_PATHS = 24, 25, 26, 27
 KERNEL_NAMES = {K_VOXELIZE: "voxelize", K_SORT: "sort", K_RAYS: "build_rays", K_INTEGRATE: "integrate",
                 K_FINALIZE: "finalize", K_MESH: "marching_cubes", K_SEGMENTS: "segments", K_BIN: "bin", K_ESDF: "esdf", K_FUSE: "fuse", K_REGISTER: "register",
                 K_REGISTER_SCORE: "register_score", K_FRONTIER_MARK: "frontier_mark", K_FRONTIER_LABEL: "frontier_label", K_FRONTIER_JOIN: "frontier_join",
                 K_FRONTIER_SUM: "frontier_sum", K_FRONTIER_EMIT: "frontier_emit", K_VIEW_GAIN: "view_gain", K_ALIGN: "align", K_ALIGN_POINTS: "align_points",
-                K_PATH_SCORE: "path_score", K_NAV_PROJECT: "nav_project", K_NAV_EDT: "nav_edt", K_NAV_EDT_ROWS: "nav_edt_rows"}
+                K_PATH_SCORE: "path_score", K_NAV_PROJECT: "nav_project", K_NAV_EDT: "nav_edt", K_NAV_EDT_ROWS: "nav_edt_rows",
+                K_NAV_FIELD_SEED: "nav_field_seed", K_NAV_FIELD_ROUND: "nav_field_round", K_NAV_FIELD_PARENT: "nav_field_parent",
+                K_NAV_FIELD_PATHS: "nav_field_paths"}
 
 
 class TsdfCfg(C.Structure):
@@ -164,6 +167,21 @@ class NavCfg(C.Structure):
                 ("reserved_", C.c_uint8 * 3)]
 
 
+class NavFieldCfg(C.Structure):
+    """tsl_nav_field_cfg (tsl_tsdf_nav_field, tsl_tsdf_nav_field_paths): B planes of H x W cells; neutral and lethal in 1 .. 255, connectivity 4 or 8, max_rounds
+    0 = 4 * tiles + 64, rounds_fixed > 0 = that many rounds and no host read, check_every 0 = 8"""
+    _fields_ = [("B", C.c_int32), ("H", C.c_int32), ("W", C.c_int32), ("neutral", C.c_int32), ("lethal", C.c_int32), ("connectivity", C.c_int32),
+                ("max_rounds", C.c_int32), ("rounds_fixed", C.c_int32), ("check_every", C.c_int32), ("reserved_", C.c_int32)]
+
+
+class NavFieldStats(C.Structure):
+    """tsl_nav_field_stats"""
+    _fields_ = [("converged", C.c_int32), ("rounds", C.c_int32), ("tile_visits", C.c_int64), ("n_bad_seeds", C.c_int32), ("reserved_", C.c_int32)]
+
+
+NAV_UNREACHED = 0xffffffff
+
+
 class TslError(RuntimeError):
     pass
 
@@ -275,6 +293,10 @@ SIGNATURES = {
     "tsl_tsdf_view_gain_dev": (C.c_int, [vp, dp, dp, i32, C.POINTER(GainCfg), vp, vp, vp, vp]),
     "tsl_tsdf_nav_grid": (C.c_int, [vp, C.POINTER(NavCfg), vp, vp, vp, vp, vp, vp]),
     "tsl_tsdf_nav_grid_dev": (C.c_int, [vp, C.POINTER(NavCfg), vp, vp, vp, vp, vp, vp, vp]),
+    "tsl_tsdf_nav_field": (C.c_int, [vp, C.POINTER(NavFieldCfg), vp, vp, i32, vp, vp, C.POINTER(NavFieldStats)]),
+    "tsl_tsdf_nav_field_dev": (C.c_int, [vp, C.POINTER(NavFieldCfg), vp, vp, i32, vp, vp, vp, vp]),
+    "tsl_tsdf_nav_field_paths": (C.c_int, [vp, C.POINTER(NavFieldCfg), vp, vp, vp, i32, i32, vp, vp, vp, vp]),
+    "tsl_tsdf_nav_field_paths_dev": (C.c_int, [vp, C.POINTER(NavFieldCfg), vp, vp, vp, i32, i32, vp, vp, vp, vp, vp]),
     "tsl_tsdf_set_option": (C.c_int, [vp, C.c_char_p, C.c_int]),
     "tsl_tsdf_get_option": (C.c_int, [vp, C.c_char_p, C.POINTER(C.c_int)]),
     "tsl_tsdf_prof_enable": (C.c_int, [vp, C.c_int]),

@@ -228,6 +228,8 @@ struct MeshIdxState;                     // tsl_mesh_indexed.hip: scratch and bu
 void mesh_indexed_release(tsl_tsdf* m);
 struct NavState;                         // tsl_nav_grid.hip: scratch and host staging of the navigation grids (allocated by the first call)
 void nav_release(tsl_tsdf* m);
+struct NavFieldState;                    // tsl_nav_field.hip: scratch, control block and pinned words of the cost-to-go fields (allocated by the first call)
+void nav_field_release(tsl_tsdf* m);
 }  // namespace tsl
 
 #define TSL_ESDF_SLOTS 4
@@ -301,6 +303,7 @@ struct tsl_tsdf {
     void* seqv_sum[TSL_NBATCH]; int* seqv_log;      // TSL_SEQ_VERIFY (developer aid, tsl_sequential.hip): per-item checksums, mismatch log
     uint32_t shape_hash; int dry_launches;      // developer statistics: FNV hash over the sizes of the batches issued so far; batches issued into a dry pipeline
     tsl::NavState* nav;                  // tsl_nav_grid.hip (allocated by the first call)
+    tsl::NavFieldState* nav_field;       // tsl_nav_field.hip (allocated by the first call)
 };
 
 namespace tsl {

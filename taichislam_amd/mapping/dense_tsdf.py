@@ -222,6 +222,7 @@ def frontier_cluster_geometry(clusters, voxel_scale):
 
 
 NAV_FREE, NAV_OCCUPIED, NAV_UNKNOWN = 0, 1, 2          # cell classes of DenseTSDF.nav_grid (TSL_NAV_* of include/taichislam_hip.h)
+NAV_UNREACHED = 0xffffffff                             # DenseTSDF.nav_field: the cell reaches no goal (TSL_NAV_UNREACHED)
 
 # tsl_path_score (include/taichislam_hip.h): 40 bytes per path
 PATH_SCORE_DTYPE = np.dtype({"names": ["n_samples", "first_stop", "n_hit", "n_unknown", "n_outside", "argmin", "min_dist", "short_update", "cost"],
@@ -1087,6 +1088,117 @@ class DenseTSDF(BaseMap):
             if v is not None:
                 out[k] = v
         return out
+
+    # ---- cost-to-go fields and paths (tsl_nav_field.hip) ------------------------------------------------
+    def nav_field(self, cost, goals, neutral=50, lethal=253, connectivity=8, parent=True, max_rounds=None, rounds_fixed=0, check_every=None, device=False):
+        """The cost-to-go field over 2-D cost planes: for every cell the least cost of getting to a goal, and which cells reach none.  cost: the `cost`
+        array of nav_grid, or the dict nav_grid returns (its cost plane is used), or any uint8 array [H, W] or [B, H, W] (1 <= H, W <= 4096, B <= 16):
+        the map is not read.  A cell is traversable when cost < lethal; moves go to the 4 or 8 neighbours (`connectivity`), a diagonal one only between
+        two traversable cells; leaving a cell costs (neutral + its cost) times 5 along an axis and 7 along a diagonal.  goals: [S, 3] = plane, row, col
+        (value 0) or [S, 4] with a start value (read as uint32); goals outside or on a wall are counted in n_bad_seeds.  Returns a dict: `field` uint32
+        [B, H, W] (NAV_UNREACHED = 2^32 - 1 where no goal is reached, sums clipped to 2^32 - 2), with parent=True `parent` u8 [B, H, W] (255 unreached,
+        8 a goal cell, else the direction code 0 .. 7 of (di, dj) = (1,0) (1,1) (0,1) (-1,1) (-1,0) (-1,-1) (0,-1) (1,-1) of the next cell), `converged`,
+        `rounds`, `tile_visits`, `n_bad_seeds`, and `goals` (int32 [S, 4]) and the parameters, for nav_paths.  The rounds stop when one changes nothing
+        (the host looks every `check_every` rounds) or at max_rounds (None = 4 * tiles of a plane + 64): then converged is 0 and the field holds upper
+        bounds.  rounds_fixed > 0 runs exactly that many rounds and reads nothing in between.  numpy in gives numpy out; torch device tensors in (or
+        device=True) give tensors out, ordered with torch.cuda.current_stream (tsl_tsdf_nav_field_dev: asynchronous with rounds_fixed > 0, and the
+        statistics are then read, which waits)."""
+        if isinstance(cost, dict):
+            cost = cost["cost"]
+        on_dev = hasattr(cost, "is_cuda")
+        if on_dev or device:
+            torch = _torch()
+            dev = torch.device(f"cuda:{self.device}")
+            ct = cost if on_dev else torch.from_numpy(np.ascontiguousarray(np.asarray(cost, dtype=np.uint8)))
+            if ct.dtype != torch.uint8:
+                raise ValueError("nav_field: cost must be uint8")
+            ct = ct.to(dev).contiguous()
+            shape = tuple(ct.shape)
+        else:
+            cost = np.asarray(cost)
+            if cost.dtype != np.uint8:
+                raise ValueError("nav_field: cost must be uint8")
+            cost = np.ascontiguousarray(cost)
+            shape = cost.shape
+        if len(shape) == 2:
+            shape = (1,) + tuple(shape)
+        if len(shape) != 3:
+            raise ValueError("nav_field: cost must be [H, W] or [B, H, W]")
+        g = goals.cpu().numpy() if hasattr(goals, "is_cuda") else np.asarray(goals)
+        if g.size == 0:
+            g = np.zeros((0, 4), np.int32)
+        if g.ndim != 2 or g.shape[1] not in (3, 4):
+            raise ValueError("nav_field: goals must be [S, 3] or [S, 4]")
+        g4 = np.zeros((g.shape[0], 4), np.int64)
+        g4[:, :g.shape[1]] = g
+        seeds = np.ascontiguousarray((g4 & 0xffffffff).astype(np.uint32).view(np.int32))
+        seeds[:, :3] = np.clip(g4[:, :3], -(1 << 31), (1 << 31) - 1).astype(np.int32)
+        cfg = _lib.NavFieldCfg()
+        cfg.B, cfg.H, cfg.W = shape
+        cfg.neutral, cfg.lethal, cfg.connectivity = int(neutral), int(lethal), int(connectivity)
+        cfg.max_rounds = 0 if max_rounds is None else int(max_rounds)
+        if max_rounds is not None and int(max_rounds) == 0:
+            raise ValueError("nav_field: max_rounds must be at least 1")
+        cfg.rounds_fixed = int(rounds_fixed)
+        cfg.check_every = 0 if check_every is None else int(check_every)
+        S = seeds.shape[0]
+        st = _lib.NavFieldStats()
+        if on_dev or device:
+            field = torch.empty(shape, dtype=getattr(torch, "uint32", torch.int32), device=dev)
+            par = torch.empty(shape, dtype=torch.uint8, device=dev) if parent else None
+            sd = torch.from_numpy(seeds).to(dev) if S else None
+            std = torch.zeros(6, dtype=torch.int32, device=dev)
+            ptr = lambda t: None if t is None else t.data_ptr()
+            _lib.check(self.L.tsl_tsdf_nav_field_dev(self.h, C.byref(cfg), ptr(ct), ptr(sd), S, ptr(field), ptr(par), ptr(std), torch.cuda.current_stream(dev).cuda_stream))
+            sv = std.cpu().numpy()
+            st.converged, st.rounds, st.n_bad_seeds = int(sv[0]), int(sv[1]), int(sv[4])
+            st.tile_visits = int(sv[2:4].view(np.int64)[0])
+        else:
+            field = np.empty(shape, np.uint32)
+            par = np.empty(shape, np.uint8) if parent else None
+            _lib.check(self.L.tsl_tsdf_nav_field(self.h, C.byref(cfg), _vp(cost), _vp(seeds) if S else None, S, _vp(field), _vp(par), C.byref(st)))
+        out = {"field": field, "converged": int(st.converged), "rounds": int(st.rounds), "tile_visits": int(st.tile_visits), "n_bad_seeds": int(st.n_bad_seeds),
+               "goals": seeds, "neutral": int(neutral), "lethal": int(lethal), "connectivity": int(connectivity)}
+        if par is not None:
+            out["parent"] = par
+        return out
+
+    def nav_paths(self, field_result, starts, max_len):
+        """The cheapest way to a goal from every start, along the parents of a nav_field result (computed with parent=True).  starts: [P, 3] = plane, row,
+        col.  One lane per start follows the parents for at most max_len cells.  Returns a dict: `cells` int16 [P, max_len, 2] = (row, col) from the
+        start on, -1 past the end; `length` int32 [P]; `status` u8 [P] (0 = ended on a goal, 1 = truncated at max_len, 2 = the start is unreached or a
+        wall, 3 = the start is outside); `cost` uint32 [P] = the field at the start.  A result of torch tensors gives tensors, asynchronously on
+        torch.cuda.current_stream (tsl_tsdf_nav_field_paths_dev); otherwise numpy arrays."""
+        if "parent" not in field_result:
+            raise ValueError("nav_paths: the field was computed without parents (nav_field(parent=True))")
+        field, par = field_result["field"], field_result["parent"]
+        s = starts.cpu().numpy() if hasattr(starts, "is_cuda") else np.asarray(starts)
+        if s.size == 0:
+            s = np.zeros((0, 3), np.int32)
+        if s.ndim != 2 or s.shape[1] != 3:
+            raise ValueError("nav_paths: starts must be [P, 3]")
+        s = np.ascontiguousarray(np.clip(s.astype(np.int64), -(1 << 31), (1 << 31) - 1).astype(np.int32))
+        P, L = s.shape[0], int(max_len)
+        cfg = _lib.NavFieldCfg()
+        cfg.B, cfg.H, cfg.W = tuple(field.shape)
+        Lc = max(L, 0)
+        if hasattr(field, "is_cuda"):
+            torch = _torch()
+            dev = field.device
+            cells = torch.empty((P, Lc, 2), dtype=torch.int16, device=dev)
+            length = torch.empty(P, dtype=torch.int32, device=dev)
+            status = torch.empty(P, dtype=torch.uint8, device=dev)
+            cost = torch.empty(P, dtype=getattr(torch, "uint32", torch.int32), device=dev)
+            sd = torch.from_numpy(s).to(dev) if P else None
+            _lib.check(self.L.tsl_tsdf_nav_field_paths_dev(self.h, C.byref(cfg), field.data_ptr(), par.data_ptr(), sd.data_ptr() if P else None, P, L, cells.data_ptr(),
+                                                           length.data_ptr(), status.data_ptr(), cost.data_ptr(), torch.cuda.current_stream(dev).cuda_stream))
+        else:
+            field, par = np.ascontiguousarray(field, dtype=np.uint32), np.ascontiguousarray(par, dtype=np.uint8)
+            cells = np.empty((P, Lc, 2), np.int16)
+            length, status, cost = np.empty(P, np.int32), np.empty(P, np.uint8), np.empty(P, np.uint32)
+            _lib.check(self.L.tsl_tsdf_nav_field_paths(self.h, C.byref(cfg), _vp(field), _vp(par), _vp(s) if P else None, P, L, _vp(cells), _vp(length), _vp(status),
+                                                       _vp(cost)))
+        return {"cells": cells, "length": length, "status": status, "cost": cost}
 
     # ---- frame-to-model alignment (tsl_align.hip, DESIGN.md section 4.8) ---------------------------------------------------
     def align_linearize(self, depth, R, T, K=None, stride=1, d_min=None, d_max=None, r_max=None, g_max=None, huber=0.0, device=False, counts_only=False):

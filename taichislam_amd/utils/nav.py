@@ -1,4 +1,4 @@
-"""Helpers around DenseTSDF.nav_grid: cost tables for its lookup."""
+"""Helpers around DenseTSDF.nav_grid and DenseTSDF.nav_field (DESIGN.md sections 4.15, 4.16): cost tables for the lookup, the reach of frontier clusters."""
 import numpy as np
 
 
@@ -20,3 +20,38 @@ def inflation_lut(voxel, radius_vox, inscribed, inflation, scale=10.0):
     lut[0] = 254.0
     lut[R * R + 1] = 0.0
     return lut.astype(np.uint8)
+
+
+NAV_UNREACHED = 0xffffffff
+
+
+def frontier_reach(frontiers, field_result, band, N=None, plane=0):
+    """Which frontier clusters can be reached, and how cheaply: per cluster of a DenseTSDF.extract_frontiers result the least value of a DenseTSDF.nav_field
+    result over the columns (i + N / 2, j + N / 2) of the cluster's voxels whose layer k lies in band = (k_min, k_max), both ends inclusive -- the band
+    the field's cost plane was projected from -- and the voxel that attains it.  N: the width of the volume (default: the height of the field's planes);
+    plane: the plane of the field to read.  Host numpy; tensors are copied.  Returns a dict: `value` uint32 [m] (NAV_UNREACHED for a cluster that has
+    no voxel in the band or reaches nothing), `voxel` int64 [m] (the row of frontiers["indices"] that attains it, the first in the frontiers' order
+    on a tie; -1 with NAV_UNREACHED), `reached` bool [m]."""
+    def host(a):
+        return np.asarray(a.cpu().numpy() if hasattr(a, "cpu") else a)
+    field = host(field_result["field"] if isinstance(field_result, dict) else field_result)
+    if field.ndim == 2:
+        field = field[None]
+    f = field[int(plane)]
+    N = int(f.shape[0] if N is None else N)
+    idx = host(frontiers["indices"]).astype(np.int64).reshape(-1, 3)
+    cl = host(frontiers["cluster"]).astype(np.int64).reshape(-1)
+    m = len(frontiers["clusters"])
+    value = np.full(m, NAV_UNREACHED, np.uint32)
+    voxel = np.full(m, -1, np.int64)
+    ui, uj = idx[:, 0] + N // 2, idx[:, 1] + N // 2
+    ok = (idx[:, 2] >= int(band[0])) & (idx[:, 2] <= int(band[1])) & (ui >= 0) & (ui < f.shape[0]) & (uj >= 0) & (uj < f.shape[1])
+    rows = np.nonzero(ok)[0]
+    if rows.size:
+        v = f[ui[rows], uj[rows]].astype(np.int64)
+        order = np.lexsort((rows, v, cl[rows]))                  # by cluster, then value, then row
+        first = order[np.concatenate([[True], np.diff(cl[rows][order]) != 0])]
+        hit = v[first] != NAV_UNREACHED
+        value[cl[rows][first][hit]] = v[first][hit].astype(np.uint32)
+        voxel[cl[rows][first][hit]] = rows[first][hit]
+    return {"value": value, "voxel": voxel, "reached": value != NAV_UNREACHED}
