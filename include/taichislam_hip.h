@@ -69,6 +69,7 @@ enum { TSL_K_VOXELIZE = 0, TSL_K_SORT = 1, TSL_K_RAYS = 2, TSL_K_INTEGRATE = 3, 
        TSL_K_FRONTIER_EMIT = 16, TSL_K_VIEW_GAIN = 17, TSL_K_ALIGN = 18, TSL_K_ALIGN_POINTS = 19, TSL_K_PATH_SCORE = 20,
        TSL_K_NAV_PROJECT = 21, TSL_K_NAV_EDT = 22, TSL_K_NAV_EDT_ROWS = 23,
        TSL_K_NAV_FIELD_SEED = 24, TSL_K_NAV_FIELD_ROUND = 25, TSL_K_NAV_FIELD_PARENT = 26, TSL_K_NAV_FIELD_PATHS = 27,
+       TSL_K_NAV_TERRAIN_COLUMNS = 28, TSL_K_NAV_TERRAIN_WINDOW = 29,
        TSL_K_COUNT };
 
 const char* tsl_version(void);
@@ -729,6 +730,60 @@ int  tsl_tsdf_nav_field_paths(tsl_tsdf* m, const tsl_nav_field_cfg* cfg, const u
                               int32_t n_starts, int32_t max_len, int16_t* cells /* [P][L][2] */, int32_t* length, uint8_t* status, uint32_t* cost);
 int  tsl_tsdf_nav_field_paths_dev(tsl_tsdf* m, const tsl_nav_field_cfg* cfg, const void* field_dev, const void* parent_dev, const void* starts_dev,
                                   int32_t n_starts, int32_t max_len, void* cells_dev, void* length_dev, void* status_dev, void* cost_dev, void* user_stream);
+
+/* ---- terrain layers for ground robots (tsl_nav_terrain.hip): per height band and (x, y) column the height of the surface a robot
+ * can stand on, over the robot's footprint the step and the slope of that surface, and a class, a distance and a cost in the vocabulary of
+ * tsl_tsdf_nav_grid, so that tsl_tsdf_nav_field and the OccupancyGrid adapters take them unchanged.  Where nav_grid calls a column an obstacle as soon as
+ * the band holds an occupied voxel, this pass tells a ramp from a wall, a kerb from a cliff and a table one fits under from a block.  The reference has
+ * no such pass.  Everything is integer except the f32 comparison of the voxel classes and one f64 expression per column: the result depends on no
+ * schedule and tests/nav_terrain_ref.py restates it bit for bit.  The pass reads one submap slot and writes nothing to the map.  All k are signed layers.
+ *   The submap slot, the voxel classes and thres are exactly those of tsl_tsdf_nav_grid: thres = free_thres, 0 = the map's surface threshold; an observed
+ *     NaN is UNKNOWN; a layer outside the volume is UNKNOWN.
+ *   Bands: n_bands in 1 .. 16, k_min[b] <= k_max[b] inside the volume, as in nav_grid: the range in which the support layer is looked for.
+ *   Standable layer: layer k of a column is standable when voxel k is OCCUPIED, none of the `clearance` layers k + 1 .. k + clearance is OCCUPIED, and all
+ *     of the `free_run` layers k + 1 .. k + free_run are FREE.  0 <= free_run <= clearance <= Nz.  The layers tested above k may leave the band; where
+ *     they leave the volume they are UNKNOWN, which is not occupied and not free.
+ *   Support: the lowest standable layer of the column with k_min <= k <= k_max when pick = 0, the highest when pick = 1.
+ *   col (u8): 0 = has a support; 1 = obstructed: the band holds an OCCUPIED voxel but no standable layer (a wall, a top without headroom); 2 = empty: no
+ *     OCCUPIED voxel in the band.
+ *   height (int16): 16 * k + q for the support layer k; 32767 where col != 0.  q in 0 .. 15 places the level set thres between the centres of layers k and
+ *     k + 1.  When voxel k + 1 is FREE: r = 16.0 * ((double)thres - (double)t_k) / ((double)t_k1 - (double)t_k), the f16 values widened exactly: three
+ *     correctly rounded IEEE f64 operations in this order; q = r >= 15.0 ? 15 : (r >= 0.0 ? (int)r : 0), so a NaN r (infinite voxels) gives 0.  When voxel
+ *     k + 1 is not FREE, q = 0.  The height is that of the iso-level thres, which lies about thres above the zero crossing of the TSDF: a constant offset
+ *     of every height (1.8 voxels = 28.8 height units at the default threshold 1.8 * voxel_scale; subtract it when absolute heights matter; steps
+ *     and slopes do not see it).  In metres a height is height * voxel / 16.  A volume with Nz > 4094 is refused: height would not fit.
+ *   Window statistics, for the cells with col == 0, over the (2 w + 1)^2 cells within Chebyshev distance w = window, 0 .. 16, clipped to the grid:
+ *     nsup (uint16) = the number of those cells that have a support; step (uint16) = the maximum minus the minimum height over them.  Both are 65535
+ *     where col != 0.
+ *   slope2 (uint32): a Sobel gradient of height at stride s = slope_base, 1 .. 16.  With h(di, dj) = height[i + di][j + dj]:
+ *     gx = h(s,-s) + 2 h(s,0) + h(s,s) - h(-s,-s) - 2 h(-s,0) - h(-s,s); gy the same with the roles of i and j exchanged;
+ *     slope2 = min(gx^2 + gy^2, 2^32 - 2), computed in 64 bits.  It is valid only when the cell and all eight cells at stride s are inside the grid and
+ *     have a support; otherwise it is 2^32 - 1.  tan of the slope = sqrt(slope2) / (128 s).
+ *   cls (u8, the codes of nav_grid), tested in this order: col == 1: TSL_NAV_OCCUPIED; col == 2: TSL_NAV_UNKNOWN; step > max_step: OCCUPIED; slope2 valid
+ *     and > max_slope2: OCCUPIED; nsup < min_support: UNKNOWN; otherwise TSL_NAV_FREE.  max_step is 0 .. 65534 sixteenths of a voxel; max_slope2 =
+ *     2^32 - 1 switches the slope test off.
+ *   d2, cost: nav_grid's own distance passes over this cls plane, with the same radius (0 .. 254), flag bits 0 and 1, lut of R * R + 2 entries and
+ *     cost_unknown, and the same values.
+ *   Layout: every plane is [B][N][N], indexed [b][i + N/2][j + N/2].  Every output is nullable on its own, and a plane that is not asked for is not
+ *     computed where that is separable: without step, nsup, slope2, cls, d2 and cost the window pass does not run; without d2 and cost the distance
+ *     passes do not run.  cost and lut come together or not at all.
+ * tsl_tsdf_nav_terrain issues the queued frames, runs on the handle's stream behind them, waits and copies back.  tsl_tsdf_nav_terrain_dev takes device
+ * pointers, is ASYNCHRONOUS and ordered with `user_stream` exactly like tsl_tsdf_nav_grid_dev.  Scratch lives on the handle, grows as needed and is
+ * released with it.  With profiling on, tsl_tsdf_prof_query returns the time of TSL_K_NAV_TERRAIN_COLUMNS (the column walk), TSL_K_NAV_TERRAIN_WINDOW (the
+ * window statistics, the slope and the class) and, for the distance passes, TSL_K_NAV_EDT_ROWS and TSL_K_NAV_EDT.
+ * TSL_ERR_ARG, before anything is launched or written (the text names the entry point): a null handle or cfg; every output null; n_bands outside
+ * 1 .. 16; a band that is empty or leaves the volume; a free_thres that is not finite; clearance outside 0 .. Nz; free_run outside 0 .. clearance; pick
+ * other than 0 or 1; window outside 0 .. 16; slope_base outside 1 .. 16; max_step outside 0 .. 65534; a negative min_support; radius outside 0 .. 254;
+ * flag bits other than 0 and 1; cost without lut or lut without cost; Nz > 4094; N * N * n_bands >= 2^31.  A refused call leaves the handle usable. */
+#define TSL_TERRAIN_NO_HEIGHT 32767
+#define TSL_TERRAIN_NO_SLOPE 0xffffffffu
+typedef struct { int32_t n_bands, k_min[16], k_max[16]; float free_thres;
+                 int32_t clearance, free_run, pick, window, slope_base, max_step, min_support; uint32_t max_slope2;
+                 int32_t radius, flags; uint8_t cost_unknown, reserved_[3]; } tsl_nav_terrain_cfg;
+int  tsl_tsdf_nav_terrain(tsl_tsdf* m, const tsl_nav_terrain_cfg* cfg, const uint8_t* lut, int16_t* height, uint8_t* col, uint16_t* step,
+                          uint16_t* nsup, uint32_t* slope2, uint8_t* cls, uint16_t* d2, uint8_t* cost);
+int  tsl_tsdf_nav_terrain_dev(tsl_tsdf* m, const tsl_nav_terrain_cfg* cfg, const void* lut_dev, void* height_dev, void* col_dev, void* step_dev,
+                              void* nsup_dev, void* slope2_dev, void* cls_dev, void* d2_dev, void* cost_dev, void* user_stream);
 
 /* backend knobs for A/B-ing kernel variants: name in
      "variant"  0|1: one global int64 atomic pair per ray step, 2 (default): brick-binned LDS accumulation

@@ -11,13 +11,14 @@ K_FRONTIER_MARK, K_FRONTIER_LABEL, K_FRONTIER_JOIN, K_FRONTIER_SUM, K_FRONTIER_E
 K_VIEW_GAIN, K_ALIGN, K_ALIGN_POINTS, K_PATH_SCORE = 17, 18, 19, 20
 K_NAV_PROJECT, K_NAV_EDT, K_NAV_EDT_ROWS = 21, 22, 23
 K_NAV_FIELD_SEED, K_NAV_FIELD_ROUND, K_NAV_FIELD_PARENT, K_NAV_FIELD_PATHS = 24, 25, 26, 27
+K_NAV_TERRAIN_COLUMNS, K_NAV_TERRAIN_WINDOW = 28, 29
 KERNEL_NAMES = {K_VOXELIZE: "voxelize", K_SORT: "sort", K_RAYS: "build_rays", K_INTEGRATE: "integrate",
                 K_FINALIZE: "finalize", K_MESH: "marching_cubes", K_SEGMENTS: "segments", K_BIN: "bin", K_ESDF: "esdf", K_FUSE: "fuse", K_REGISTER: "register",
                 K_REGISTER_SCORE: "register_score", K_FRONTIER_MARK: "frontier_mark", K_FRONTIER_LABEL: "frontier_label", K_FRONTIER_JOIN: "frontier_join",
                 K_FRONTIER_SUM: "frontier_sum", K_FRONTIER_EMIT: "frontier_emit", K_VIEW_GAIN: "view_gain", K_ALIGN: "align", K_ALIGN_POINTS: "align_points",
                 K_PATH_SCORE: "path_score", K_NAV_PROJECT: "nav_project", K_NAV_EDT: "nav_edt", K_NAV_EDT_ROWS: "nav_edt_rows",
                 K_NAV_FIELD_SEED: "nav_field_seed", K_NAV_FIELD_ROUND: "nav_field_round", K_NAV_FIELD_PARENT: "nav_field_parent",
-                K_NAV_FIELD_PATHS: "nav_field_paths"}
+                K_NAV_FIELD_PATHS: "nav_field_paths", K_NAV_TERRAIN_COLUMNS: "nav_terrain_columns", K_NAV_TERRAIN_WINDOW: "nav_terrain_window"}
 
 
 class TsdfCfg(C.Structure):
@@ -182,6 +183,19 @@ class NavFieldStats(C.Structure):
 NAV_UNREACHED = 0xffffffff
 
 
+class NavTerrainCfg(C.Structure):
+    """tsl_nav_terrain_cfg (tsl_tsdf_nav_terrain): the bands and free_thres of tsl_nav_cfg; clearance and free_run in layers above the support, pick 0 = the
+    lowest / 1 = the highest standable layer, window and slope_base in cells, max_step in sixteenths of a voxel, max_slope2 = (tan * 128 * slope_base)^2
+    (2^32 - 1 = no limit); radius, flags and cost_unknown as in tsl_nav_cfg"""
+    _fields_ = [("n_bands", C.c_int32), ("k_min", C.c_int32 * 16), ("k_max", C.c_int32 * 16), ("free_thres", C.c_float), ("clearance", C.c_int32),
+                ("free_run", C.c_int32), ("pick", C.c_int32), ("window", C.c_int32), ("slope_base", C.c_int32), ("max_step", C.c_int32),
+                ("min_support", C.c_int32), ("max_slope2", C.c_uint32), ("radius", C.c_int32), ("flags", C.c_int32), ("cost_unknown", C.c_uint8),
+                ("reserved_", C.c_uint8 * 3)]
+
+
+TERRAIN_NO_HEIGHT, TERRAIN_NO_STAT, TERRAIN_NO_SLOPE = 32767, 65535, 0xffffffff
+
+
 class TslError(RuntimeError):
     pass
 
@@ -297,6 +311,8 @@ SIGNATURES = {
     "tsl_tsdf_nav_field_dev": (C.c_int, [vp, C.POINTER(NavFieldCfg), vp, vp, i32, vp, vp, vp, vp]),
     "tsl_tsdf_nav_field_paths": (C.c_int, [vp, C.POINTER(NavFieldCfg), vp, vp, vp, i32, i32, vp, vp, vp, vp]),
     "tsl_tsdf_nav_field_paths_dev": (C.c_int, [vp, C.POINTER(NavFieldCfg), vp, vp, vp, i32, i32, vp, vp, vp, vp, vp]),
+    "tsl_tsdf_nav_terrain": (C.c_int, [vp, C.POINTER(NavTerrainCfg), vp, vp, vp, vp, vp, vp, vp, vp, vp]),
+    "tsl_tsdf_nav_terrain_dev": (C.c_int, [vp, C.POINTER(NavTerrainCfg), vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
     "tsl_tsdf_set_option": (C.c_int, [vp, C.c_char_p, C.c_int]),
     "tsl_tsdf_get_option": (C.c_int, [vp, C.c_char_p, C.POINTER(C.c_int)]),
     "tsl_tsdf_prof_enable": (C.c_int, [vp, C.c_int]),

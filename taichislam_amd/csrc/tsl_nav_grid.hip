@@ -243,6 +243,22 @@ static int nav_check(tsl_tsdf* m, const tsl_nav_cfg* c, const void* lut, const v
 
 #define NAV_GROW(field, bytes_field, bytes) do { if ((rc = grow(&S->field, &S->bytes_field, (bytes)))) return rc; } while (0)
 
+// the two distance passes on q over a class plane [B][N][N] (g: B * N * N bytes of scratch); tsl_nav_terrain.hip runs them over its own classes
+int nav_edt_launch(tsl_tsdf* m, hipStream_t q, int N, int B, int R, int flags, int cost_unknown, const uint8_t* cls, uint8_t* g, const uint8_t* lut, uint16_t* d2,
+                   uint8_t* cost)
+{
+    const int words = (N + 63) / 64, rows = N * B;
+    prof_begin(m, TSL_K_NAV_EDT_ROWS, q);
+    hipLaunchKernelGGL(k_nav_rows, dim3((unsigned)((rows + 3) / 4)), dim3(256), sizeof(unsigned long long) * 4 * (size_t)words, q, N, rows, R, flags, words, cls, g);
+    prof_end(m, q);
+    prof_begin(m, TSL_K_NAV_EDT, q);
+    hipLaunchKernelGGL(k_nav_cols, dim3((unsigned)((N + NAV_TILE - 1) / NAV_TILE), (unsigned)((N + NAV_ROWS - 1) / NAV_ROWS), (unsigned)B), dim3(256),
+                       (size_t)(NAV_ROWS + 2 * R) * NAV_TILE, q, N, R, flags, cost_unknown, (const uint8_t*)g, cls, lut, d2, cost);
+    prof_end(m, q);
+    TSL_HIP(hipGetLastError());
+    return TSL_OK;
+}
+
 // the three launches on q; every pointer a device pointer, null planes skipped
 static int nav_launch(tsl_tsdf* m, hipStream_t q, const NavCfg& C, const uint8_t* lut, uint8_t* cls, uint16_t* d2, uint8_t* cost, uint16_t* counts, int16_t* span)
 {
@@ -262,19 +278,7 @@ static int nav_launch(tsl_tsdf* m, hipStream_t q, const NavCfg& C, const uint8_t
         prof_end(m, q);
         TSL_HIP(hipGetLastError());
     }
-    if (edt) {
-        const int words = (N + 63) / 64, rows = N * C.B;
-        prof_begin(m, TSL_K_NAV_EDT_ROWS, q);
-        hipLaunchKernelGGL(k_nav_rows, dim3((unsigned)((rows + 3) / 4)), dim3(256), sizeof(unsigned long long) * 4 * (size_t)words, q, N, rows, C.R, C.flags, words,
-                           cls, (uint8_t*)S->g);
-        prof_end(m, q);
-        prof_begin(m, TSL_K_NAV_EDT, q);
-        hipLaunchKernelGGL(k_nav_cols, dim3((unsigned)((N + NAV_TILE - 1) / NAV_TILE), (unsigned)((N + NAV_ROWS - 1) / NAV_ROWS), (unsigned)C.B), dim3(256),
-                           (size_t)(NAV_ROWS + 2 * C.R) * NAV_TILE, q, N, C.R, C.flags, C.cost_unknown,
-                           (const uint8_t*)S->g, cls, lut, d2, cost);
-        prof_end(m, q);
-        TSL_HIP(hipGetLastError());
-    }
+    if (edt) return nav_edt_launch(m, q, N, C.B, C.R, C.flags, C.cost_unknown, cls, (uint8_t*)S->g, lut, d2, cost);
     return TSL_OK;
 }
 

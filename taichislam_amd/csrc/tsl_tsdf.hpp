@@ -230,6 +230,8 @@ struct NavState;                         // tsl_nav_grid.hip: scratch and host s
 void nav_release(tsl_tsdf* m);
 struct NavFieldState;                    // tsl_nav_field.hip: scratch, control block and pinned words of the cost-to-go fields (allocated by the first call)
 void nav_field_release(tsl_tsdf* m);
+struct NavTerrainState;                  // tsl_nav_terrain.hip: scratch and host staging of the terrain layers (allocated by the first call)
+void nav_terrain_release(tsl_tsdf* m);
 }  // namespace tsl
 
 #define TSL_ESDF_SLOTS 4
@@ -304,6 +306,7 @@ struct tsl_tsdf {
     uint32_t shape_hash; int dry_launches;      // developer statistics: FNV hash over the sizes of the batches issued so far; batches issued into a dry pipeline
     tsl::NavState* nav;                  // tsl_nav_grid.hip (allocated by the first call)
     tsl::NavFieldState* nav_field;       // tsl_nav_field.hip (allocated by the first call)
+    tsl::NavTerrainState* nav_terrain;   // tsl_nav_terrain.hip (allocated by the first call)
 };
 
 namespace tsl {
@@ -326,6 +329,8 @@ int  launch_seq_apply(tsl_tsdf* m, const BatchDev& B, const FrameParams& P, int 
 void seq_release(tsl_tsdf* m);
 int  order_before(tsl_tsdf* m, hipStream_t user, hipStream_t q);         // tsl_query.hip: device-buffer queries run on the handle's stream after `user`'s work ...
 int  order_after(tsl_tsdf* m, hipStream_t user, hipStream_t q);          // ... and `user` waits for them
+int  nav_edt_launch(tsl_tsdf* m, hipStream_t q, int N, int B, int R, int flags, int cost_unknown, const uint8_t* cls, uint8_t* g, const uint8_t* lut, uint16_t* d2,
+                    uint8_t* cost);                                      // tsl_nav_grid.hip: the two distance passes (and the cost lookup) over a class plane
 int  seq_prepare(tsl_tsdf* m);
 int  selftest_seqdiv(unsigned long long* bad_dev);
 int  seq_verify_report(tsl_tsdf* m, int* out, int cap);

@@ -223,6 +223,7 @@ def frontier_cluster_geometry(clusters, voxel_scale):
 
 NAV_FREE, NAV_OCCUPIED, NAV_UNKNOWN = 0, 1, 2          # cell classes of DenseTSDF.nav_grid (TSL_NAV_* of include/taichislam_hip.h)
 NAV_UNREACHED = 0xffffffff                             # DenseTSDF.nav_field: the cell reaches no goal (TSL_NAV_UNREACHED)
+TERRAIN_NO_HEIGHT, TERRAIN_NO_STAT, TERRAIN_NO_SLOPE = 32767, 65535, 0xffffffff      # DenseTSDF.nav_terrain: no support / no window statistics / no valid slope
 
 # tsl_path_score (include/taichislam_hip.h): 40 bytes per path
 PATH_SCORE_DTYPE = np.dtype({"names": ["n_samples", "first_stop", "n_hit", "n_unknown", "n_outside", "argmin", "min_dist", "short_update", "cost"],
@@ -1199,6 +1200,87 @@ class DenseTSDF(BaseMap):
             _lib.check(self.L.tsl_tsdf_nav_field_paths(self.h, C.byref(cfg), _vp(field), _vp(par), _vp(s) if P else None, P, L, _vp(cells), _vp(length), _vp(status),
                                                        _vp(cost)))
         return {"cells": cells, "length": length, "status": status, "cost": cost}
+
+    # ---- terrain layers for ground robots (tsl_nav_terrain.hip) ------------------------------------------
+    def nav_terrain(self, bands=None, z_range=None, clearance=1.0, free_run=1, pick="lowest", window=0.2, slope_base=None, max_step=0.1, max_slope_deg=None,
+                    min_support=1, radius=1.0, unknown_is_obstacle=False, wall_is_obstacle=False, lut=None, cost_unknown=255, free_thres=None, device=False):
+        """The layer between the 3-D map and a ground robot's 2-D planner: per band (bands / z_range as in nav_grid: the range in which the surface is looked
+        for) and (x, y) column the height of the surface the robot can stand on, over its footprint the step and the slope of that surface, and a class,
+        a distance and a cost in nav_grid's vocabulary -- nav_field, nav_paths, frontier_reach and ros_adapters.occupancy_grid_fields take the result as
+        they take nav_grid's.  A layer k is standable when its voxel is occupied, none of the layers up to `clearance` (metres, rounded to layers) above
+        it is occupied and the `free_run` layers (a count) directly above it are free; the support is the lowest (pick="lowest") or the highest
+        ("highest") standable layer of the band.  `col`: 0 = the column has a support, 1 = obstructed (occupied voxels but nowhere to stand: a wall, a
+        top without headroom), 2 = empty.  `height` int16 = 16 * k + q, q in 0 .. 15 the sub-voxel place of the surface level (free_thres as in
+        nav_grid) between layers k and k + 1; TERRAIN_NO_HEIGHT = 32767 without a support; in metres height * height_unit.  Over the cells within
+        `window` (metres, rounded to cells, at most 16; Chebyshev) `nsup` counts the supported ones and `step` is the largest minus the smallest
+        height (65535 = TERRAIN_NO_STAT on a cell without a support).  `slope2` is a Sobel gradient at stride `slope_base` (metres, rounded to 1 .. 16
+        cells; None = the window, at least one cell): tan(slope) = sqrt(slope2) / (128 * stride), TERRAIN_NO_SLOPE = 2^32 - 1 where a cell of the stencil
+        is outside the grid or has no support.  `cls`: obstructed -> NAV_OCCUPIED, empty -> NAV_UNKNOWN, step > max_step (metres; None = no limit) ->
+        occupied, slope above max_slope_deg (None = no limit) -> occupied, fewer than min_support supported cells in the window -> unknown, else
+        NAV_FREE.  radius, unknown_is_obstacle, wall_is_obstacle, lut and cost_unknown are nav_grid's and give `d2` and, with lut, `cost` over these
+        classes.  Returns a dict of the planes height, col, step, nsup, slope2, cls, d2[, cost], each [B, N, N] indexed [b][i + N / 2][j + N / 2], and
+        `voxel`, `origin_xy`, `bands`, `radius_vox`, `height_unit` = voxel / 16 and the integer limits that were passed: `clearance_vox`, `free_run`,
+        `pick`, `window_vox`, `slope_base_vox`, `max_step_units`, `max_slope2`, `min_support`.  device=True returns the planes as torch tensors on the
+        map's device, asynchronously, ordered with torch.cuda.current_stream (tsl_tsdf_nav_terrain_dev); otherwise numpy arrays."""
+        bl = self._nav_bands(bands, z_range)
+        vs = float(self.voxel_scale)
+
+        def cells_of(name, x):
+            x = float(x)
+            if not math.isfinite(x) or x < 0.0:
+                raise ValueError(f"nav_terrain: {name} must be finite and not negative")
+            return int(round(x / vs))
+        R, cl, w = cells_of("radius", radius), cells_of("clearance", clearance), cells_of("window", window)
+        s = max(1, min(16, w)) if slope_base is None else max(1, cells_of("slope_base", slope_base))
+        if pick not in ("lowest", "highest"):
+            raise ValueError("nav_terrain: pick must be 'lowest' or 'highest'")
+        if max_step is None:
+            ms = 65534
+        else:
+            max_step = float(max_step)
+            if not math.isfinite(max_step) or max_step < 0.0:
+                raise ValueError("nav_terrain: max_step must be finite and not negative")
+            ms = min(65534, int(round(max_step / vs * 16.0)))
+        from ..utils.nav import terrain_slope2
+        ms2 = terrain_slope2(max_slope_deg, min(s, 16))
+        if free_thres is not None and not float(free_thres) > 0.0:
+            raise ValueError("nav_terrain: free_thres must be positive")
+        cfg = _lib.NavTerrainCfg()
+        cfg.n_bands = len(bl)
+        for b, (k0, k1) in enumerate(bl):
+            cfg.k_min[b], cfg.k_max[b] = k0, k1
+        cfg.free_thres = 0.0 if free_thres is None else float(free_thres)
+        cfg.clearance, cfg.free_run, cfg.pick, cfg.window, cfg.slope_base = cl, int(free_run), 0 if pick == "lowest" else 1, w, s
+        cfg.max_step, cfg.min_support, cfg.max_slope2 = ms, int(min_support), ms2
+        cfg.radius = R
+        cfg.flags = (1 if unknown_is_obstacle else 0) | (2 if wall_is_obstacle else 0)
+        cfg.cost_unknown = int(cost_unknown) & 0xff
+        if lut is not None:
+            lut = np.ascontiguousarray(np.asarray(lut, dtype=np.uint8).reshape(-1))
+            if lut.size != R * R + 2:
+                raise ValueError(f"nav_terrain: lut must hold R * R + 2 = {R * R + 2} entries, not {lut.size}")
+        B, N = len(bl), self.N
+        out = {"voxel": vs, "origin_xy": (-(N // 2) - 0.5) * vs, "bands": bl, "radius_vox": R, "height_unit": vs / 16.0, "clearance_vox": cl,
+               "free_run": int(free_run), "pick": pick, "window_vox": w, "slope_base_vox": s, "max_step_units": ms, "max_slope2": ms2, "min_support": int(min_support)}
+        names = ("height", "col", "step", "nsup", "slope2", "cls", "d2") + (("cost",) if lut is not None else ())
+        if device:
+            torch = _torch()
+            dev = torch.device(f"cuda:{self.device}")
+            u16 = _DEPTH_DTYPES(torch)[1]
+            kinds = {"height": torch.int16, "col": torch.uint8, "step": u16, "nsup": u16, "slope2": getattr(torch, "uint32", torch.int32), "cls": torch.uint8,
+                     "d2": u16, "cost": torch.uint8}
+            pl = {k: torch.empty((B, N, N), dtype=kinds[k], device=dev) for k in names}
+            lut_d = torch.from_numpy(lut).to(dev) if lut is not None else None
+            p = lambda k: pl[k].data_ptr() if k in pl else None
+            _lib.check(self.L.tsl_tsdf_nav_terrain_dev(self.h, C.byref(cfg), None if lut_d is None else lut_d.data_ptr(), p("height"), p("col"), p("step"), p("nsup"),
+                                                       p("slope2"), p("cls"), p("d2"), p("cost"), torch.cuda.current_stream(dev).cuda_stream))
+        else:
+            kinds = {"height": np.int16, "col": np.uint8, "step": np.uint16, "nsup": np.uint16, "slope2": np.uint32, "cls": np.uint8, "d2": np.uint16, "cost": np.uint8}
+            pl = {k: np.empty((B, N, N), kinds[k]) for k in names}
+            p = lambda k: _vp(pl[k]) if k in pl else None
+            _lib.check(self.L.tsl_tsdf_nav_terrain(self.h, C.byref(cfg), _vp(lut), p("height"), p("col"), p("step"), p("nsup"), p("slope2"), p("cls"), p("d2"), p("cost")))
+        out.update(pl)
+        return out
 
     # ---- frame-to-model alignment (tsl_align.hip, DESIGN.md section 4.8) ---------------------------------------------------
     def align_linearize(self, depth, R, T, K=None, stride=1, d_min=None, d_max=None, r_max=None, g_max=None, huber=0.0, device=False, counts_only=False):

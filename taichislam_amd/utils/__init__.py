@@ -1,1 +1,1 @@
-from .nav import frontier_reach, inflation_lut  # noqa: F401
+from .nav import frontier_reach, inflation_lut, terrain_slope2, terrain_slope_deg  # noqa: F401

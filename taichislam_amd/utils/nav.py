@@ -22,6 +22,28 @@ def inflation_lut(voxel, radius_vox, inscribed, inflation, scale=10.0):
     return lut.astype(np.uint8)
 
 
+def terrain_slope2(max_slope_deg, slope_base_vox):
+    """The max_slope2 of DenseTSDF.nav_terrain for a slope limit in degrees at a Sobel stride of slope_base_vox cells: floor((tan(deg) * 128 * s)^2),
+    at most 2^32 - 2; None = 2^32 - 1, which switches the test off."""
+    if max_slope_deg is None:
+        return 0xffffffff
+    deg, s = float(max_slope_deg), int(slope_base_vox)
+    if not 0.0 <= deg < 90.0 or not 1 <= s <= 16:
+        raise ValueError("terrain_slope2: needs 0 <= max_slope_deg < 90 and a stride of 1 .. 16 cells")
+    return min(0xfffffffe, int(np.floor((np.tan(np.radians(deg)) * 128.0 * s) ** 2)))
+
+
+def terrain_slope_deg(slope2, slope_base_vox):
+    """The slope in degrees (float64) of the `slope2` plane of DenseTSDF.nav_terrain: atan(sqrt(slope2) / (128 * s)); NaN where slope2 is 2^32 - 1 (no
+    valid stencil).  Host numpy; tensors are copied."""
+    a = np.asarray(slope2.cpu().numpy() if hasattr(slope2, "cpu") else slope2)
+    if a.dtype == np.int32:                                      # a torch build without uint32 hands the bits over as int32
+        a = a.view(np.uint32)
+    a = a.astype(np.uint32)
+    d =np.degrees(np.arctan(np.sqrt(a.astype(np.float64)) / (128.0 * int(slope_base_vox))))
+    return np.where(a == 0xffffffff, np.nan, d)
+
+
 NAV_UNREACHED = 0xffffffff
 
 
