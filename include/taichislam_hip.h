@@ -731,6 +731,64 @@ int  tsl_tsdf_nav_field_paths(tsl_tsdf* m, const tsl_nav_field_cfg* cfg, const u
 int  tsl_tsdf_nav_field_paths_dev(tsl_tsdf* m, const tsl_nav_field_cfg* cfg, const void* field_dev, const void* parent_dev, const void* starts_dev,
                                   int32_t n_starts, int32_t max_len, void* cells_dev, void* length_dev, void* status_dev, void* cost_dev, void* user_stream);
 
+/* ---- cost-to-go fields and paths over 3-D cost volumes (tsl_nav_field3.hip): tsl_tsdf_nav_field carried into 3-D for platforms
+ * that fly -- how expensive it is to get from every cell of a volume to the nearest goal, along which cells, and which cells reach no goal, where the
+ * way may climb over a wall or drop through a stairwell.  The volume is the CALLER'S: u8 [D][H][W], indexed as layer k (z), row i (x) and column j (y) --
+ * the row and column of tsl_tsdf_nav_grid's planes with the layer in front -- 1 <= D, H, W <= 1024 and D * H * W <= 2^27; usually the ESDF sampled at a
+ * stride of a few voxels (DenseTSDF.flight_volume).  The handle supplies only the device, the stream and scratch (allocated by the first call, released
+ * with the handle); no map is read.  Everything is integer and the answer is the one minimum of a sum of positive integers: it depends on no schedule,
+ * and tests/nav_field3d_ref.py restates it bit for bit.
+ *   Traversable: cost < lethal; lethal in 1 .. 255.  neutral in 1 .. 255.
+ *   Moves: connectivity 6, 18 or 26.  Direction codes 0 .. 25 are (dk, di, dj): codes 0 .. 7 have dk = 0 and the (di, dj) of tsl_tsdf_nav_field's codes
+ *     0 .. 7, in that order; code 8 = (1, 0, 0) and codes 9 .. 16 = (1, the same eight (di, dj)); code 17 = (-1, 0, 0) and codes 18 .. 25 = (-1, the same
+ *     eight).  Connectivity 6 has the six codes with one non-zero component, 18 adds those with two, 26 has all.  Step length s = 5, 7 or 9 for one, two
+ *     or three non-zero components (the <5, 7, 9> chamfer: a volume with D = 1 is tsl_tsdf_nav_field's problem).  No corner cutting: a move from x by
+ *     (dk, di, dj) is allowed only when EVERY cell x + (a dk, b di, c dj) with a, b, c in {0, 1} is inside the volume and traversable -- the two other
+ *     cells of the square for a face diagonal, the six other cells of the cube for a space diagonal.
+ *   Seeds: int32 [S][4] = { layer, row, col, value }, 0 <= S <= 65536, value read as uint32 (2^32 - 1 counts as 2^32 - 2).  A seed outside the volume or
+ *     on a cell that is not traversable is ignored and counted in n_bad_seeds; of several seeds on one cell the least value counts.  S = 0 is no error:
+ *     everything is unreached.
+ *   field (uint32 [D][H][W]): the minimum over all move sequences x = c0, c1, .., cm = a seed cell through traversable cells of
+ *     value(seed) + sum over t < m of s(c_t -> c_t+1) * (neutral + cost[c_t]) -- the cell that is left pays -- clipped to 2^32 - 2; TSL_NAV_UNREACHED where
+ *     no seed is reached (walls included).
+ *   parent (u8 [D][H][W], nullable; a pass of its own after the rounds): 255 for an unreached cell; TSL_NAV3_SEED = 26 for a cell whose field equals a
+ *     seed value placed on it; otherwise the lowest direction code d whose move is allowed and whose neighbour n satisfies
+ *     min(field[n] + s_d * (neutral + cost[x]), 2^32 - 2) == field[x].  (Only a field that did not converge has reached cells that no neighbour
+ *     explains; they get 255.)
+ *   Rounds: one round is one launch; a tile (16 x 8 x 8 cells in j, i, k) that is marked active relaxes in LDS against a one-cell halo, writes its own
+ *     cells back and marks the neighbours whose halo changed for the next round.  No workgroup waits for another and every loop in a kernel has a bound
+ *     known at launch.  The host ends the rounds: every check_every rounds (0 = 8) it reads 4 bytes, the marks the last round made, and stops after a
+ *     round that marked nothing or at max_rounds (0 = min(4 * tiles of the volume + 64, 65536)).  Not converged is converged = 0 WITH TSL_OK -- the
+ *     field then holds upper bounds, each the cost of a real move sequence -- and never a wait.  With rounds_fixed > 0 exactly that many rounds are
+ *     enqueued and nothing is read; rounds_fixed = the `rounds` of an earlier call on the same input ends on converged = 1 (field and parent depend on no
+ *     schedule; the round count can: a halo read that meets a neighbour's write-back saves work, so where not all tiles of a round run at once read
+ *     converged).
+ *   Statistics: converged; rounds = the last round that visited a tile, counted from 1; tile_visits; n_bad_seeds.
+ * tsl_tsdf_nav_field3 takes host pointers, runs on the handle's stream, waits and copies back.  tsl_tsdf_nav_field3_dev takes device pointers (stats_dev:
+ * a tsl_nav_field3_stats in device memory, nullable) and is ordered with `user_stream` like tsl_tsdf_nav_field_dev: with rounds_fixed > 0 it is
+ * ASYNCHRONOUS; with rounds_fixed = 0 it SYNCHRONISES the handle's stream at each check, and so waits for the work of `user_stream` queued before it.
+ *   Paths (tsl_tsdf_nav_field3_paths / _dev; cfg gives D, H, W): starts int32 [P][3] = { layer, row, col }, 0 <= P <= 2^20, P * L <= 2^28.  One lane per
+ *     start follows `parent` for at most L = max_len cells.  cells int16 [P][L][3] = (layer, row, col) from the start on, rows past the end -1; length
+ *     int32 [P]; status u8 [P]: 0 = ended on a seed, 1 = truncated at L, 2 = the start is unreached or not traversable (or the parents lead nowhere: a
+ *     volume that is not of this field), 3 = the start is outside; cost uint32 [P] = the field at the start (TSL_NAV_UNREACHED for status 3).  Every
+ *     output is nullable.  The _dev form is asynchronous.
+ * These kernels have no tsl_tsdf_prof_query id; time them with events around the _dev call with rounds_fixed set (tools/bench_nav_field3d.py).
+ * TSL_ERR_ARG, before anything is launched or written (the text names the entry point): a null handle, cfg, cost or field (paths: field or parent); D, H
+ * or W outside 1 .. 1024 or more than 2^27 cells; S outside 0 .. 65536 (P outside 0 .. 2^20, P * L above 2^28); neutral or lethal outside 1 .. 255; a
+ * connectivity other than 6, 18 and 26; seeds null while S > 0 (starts while P > 0); max_len < 1; a negative max_rounds, rounds_fixed or check_every.  A
+ * refused call leaves the handle usable. */
+#define TSL_NAV3_SEED 26
+typedef struct { int32_t D, H, W, neutral, lethal, connectivity, max_rounds, rounds_fixed, check_every, reserved_; } tsl_nav_field3_cfg;
+typedef struct { int32_t converged, rounds; int64_t tile_visits; int32_t n_bad_seeds, reserved_; } tsl_nav_field3_stats;
+int  tsl_tsdf_nav_field3(tsl_tsdf* m, const tsl_nav_field3_cfg* cfg, const uint8_t* cost, const int32_t* seeds /* [S][4] */, int32_t n_seeds, uint32_t* field,
+                         uint8_t* parent, tsl_nav_field3_stats* stats);
+int  tsl_tsdf_nav_field3_dev(tsl_tsdf* m, const tsl_nav_field3_cfg* cfg, const void* cost_dev, const void* seeds_dev, int32_t n_seeds, void* field_dev,
+                             void* parent_dev, void* stats_dev, void* user_stream);
+int  tsl_tsdf_nav_field3_paths(tsl_tsdf* m, const tsl_nav_field3_cfg* cfg, const uint32_t* field, const uint8_t* parent, const int32_t* starts /* [P][3] */,
+                               int32_t n_starts, int32_t max_len, int16_t* cells /* [P][L][3] */, int32_t* length, uint8_t* status, uint32_t* cost);
+int  tsl_tsdf_nav_field3_paths_dev(tsl_tsdf* m, const tsl_nav_field3_cfg* cfg, const void* field_dev, const void* parent_dev, const void* starts_dev,
+                                   int32_t n_starts, int32_t max_len, void* cells_dev, void* length_dev, void* status_dev, void* cost_dev, void* user_stream);
+
 /* ---- terrain layers for ground robots (tsl_nav_terrain.hip): per height band and (x, y) column the height of the surface a robot
  * can stand on, over the robot's footprint the step and the slope of that surface, and a class, a distance and a cost in the vocabulary of
  * tsl_tsdf_nav_grid, so that tsl_tsdf_nav_field and the OccupancyGrid adapters take them unchanged.  Where nav_grid calls a column an obstacle as soon as

@@ -183,6 +183,21 @@ class NavFieldStats(C.Structure):
 NAV_UNREACHED = 0xffffffff
 
 
+class NavField3Cfg(C.Structure):
+    """tsl_nav_field3_cfg (tsl_tsdf_nav_field3, tsl_tsdf_nav_field3_paths): a volume of D layers of H x W cells; neutral and lethal in 1 .. 255, connectivity
+    6, 18 or 26, max_rounds 0 = min(4 * tiles + 64, 65536), rounds_fixed > 0 = that many rounds and no host read, check_every 0 = 8"""
+    _fields_ = [("D", C.c_int32), ("H", C.c_int32), ("W", C.c_int32), ("neutral", C.c_int32), ("lethal", C.c_int32), ("connectivity", C.c_int32),
+                ("max_rounds", C.c_int32), ("rounds_fixed", C.c_int32), ("check_every", C.c_int32), ("reserved_", C.c_int32)]
+
+
+class NavField3Stats(C.Structure):
+    """tsl_nav_field3_stats (the layout of tsl_nav_field_stats)"""
+    _fields_ = [("converged", C.c_int32), ("rounds", C.c_int32), ("tile_visits", C.c_int64), ("n_bad_seeds", C.c_int32), ("reserved_", C.c_int32)]
+
+
+NAV3_SEED = 26                  # TSL_NAV3_SEED: the parent code of a goal cell of DenseTSDF.nav_field3d
+
+
 class NavTerrainCfg(C.Structure):
     """tsl_nav_terrain_cfg (tsl_tsdf_nav_terrain): the bands and free_thres of tsl_nav_cfg; clearance and free_run in layers above the support, pick 0 = the
     lowest / 1 = the highest standable layer, window and slope_base in cells, max_step in sixteenths of a voxel, max_slope2 = (tan * 128 * slope_base)^2
@@ -311,6 +326,10 @@ SIGNATURES = {
     "tsl_tsdf_nav_field_dev": (C.c_int, [vp, C.POINTER(NavFieldCfg), vp, vp, i32, vp, vp, vp, vp]),
     "tsl_tsdf_nav_field_paths": (C.c_int, [vp, C.POINTER(NavFieldCfg), vp, vp, vp, i32, i32, vp, vp, vp, vp]),
     "tsl_tsdf_nav_field_paths_dev": (C.c_int, [vp, C.POINTER(NavFieldCfg), vp, vp, vp, i32, i32, vp, vp, vp, vp, vp]),
+    "tsl_tsdf_nav_field3": (C.c_int, [vp, C.POINTER(NavField3Cfg), vp, vp, i32, vp, vp, C.POINTER(NavField3Stats)]),
+    "tsl_tsdf_nav_field3_dev": (C.c_int, [vp, C.POINTER(NavField3Cfg), vp, vp, i32, vp, vp, vp, vp]),
+    "tsl_tsdf_nav_field3_paths": (C.c_int, [vp, C.POINTER(NavField3Cfg), vp, vp, vp, i32, i32, vp, vp, vp, vp]),
+    "tsl_tsdf_nav_field3_paths_dev": (C.c_int, [vp, C.POINTER(NavField3Cfg), vp, vp, vp, i32, i32, vp, vp, vp, vp, vp]),
     "tsl_tsdf_nav_terrain": (C.c_int, [vp, C.POINTER(NavTerrainCfg), vp, vp, vp, vp, vp, vp, vp, vp, vp]),
     "tsl_tsdf_nav_terrain_dev": (C.c_int, [vp, C.POINTER(NavTerrainCfg), vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
     "tsl_tsdf_set_option": (C.c_int, [vp, C.c_char_p, C.c_int]),

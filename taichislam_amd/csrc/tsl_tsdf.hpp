@@ -232,6 +232,8 @@ struct NavFieldState;                    // tsl_nav_field.hip: scratch, control 
 void nav_field_release(tsl_tsdf* m);
 struct NavTerrainState;                  // tsl_nav_terrain.hip: scratch and host staging of the terrain layers (allocated by the first call)
 void nav_terrain_release(tsl_tsdf* m);
+struct NavField3State;                   // tsl_nav_field3.hip: scratch, control block and pinned words of the 3-D cost-to-go fields (allocated by the first call)
+void nav_field3_release(tsl_tsdf* m);
 }  // namespace tsl
 
 #define TSL_ESDF_SLOTS 4
@@ -307,6 +309,7 @@ struct tsl_tsdf {
     tsl::NavState* nav;                  // tsl_nav_grid.hip (allocated by the first call)
     tsl::NavFieldState* nav_field;       // tsl_nav_field.hip (allocated by the first call)
     tsl::NavTerrainState* nav_terrain;   // tsl_nav_terrain.hip (allocated by the first call)
+    tsl::NavField3State* nav_field3;     // tsl_nav_field3.hip (allocated by the first call)
 };
 
 namespace tsl {

@@ -1201,6 +1201,164 @@ class DenseTSDF(BaseMap):
                                                        _vp(cost)))
         return {"cells": cells, "length": length, "status": status, "cost": cost}
 
+    # ---- 3-D cost-to-go fields and paths over flight volumes (tsl_nav_field3.hip) -----------------------
+    def nav_field3d(self, cost, goals, neutral=50, lethal=253, connectivity=26, parent=True, max_rounds=None, rounds_fixed=0, check_every=None, device=False):
+        """nav_field in 3-D: the cost-to-go field over a cost volume, for platforms that fly.  cost: a uint8 array [D, H, W] (layer k = z, row i = x,
+        column j = y; 1 <= D, H, W <= 1024, at most 2^27 cells) or the dict flight_volume returns: the map is not read.  A cell is traversable when
+        cost < lethal; moves go to the 6, 18 or 26 neighbours (`connectivity`), a diagonal one only when every cell of the square or cube it spans is
+        traversable; leaving a cell costs (neutral + its cost) times 5, 7 or 9 for a move with one, two or three non-zero components.  goals: [S, 3] =
+        layer, row, col (value 0) or [S, 4] with a start value (read as uint32); goals outside or on a wall are counted in n_bad_seeds.  Returns a dict
+        like nav_field's: `field` uint32 [D, H, W] (NAV_UNREACHED where no goal is reached, sums clipped to 2^32 - 2), with parent=True `parent` u8
+        [D, H, W] (255 unreached, 26 = _lib.NAV3_SEED a goal cell, else the direction code 0 .. 25 of the next cell: 0 .. 7 nav_field's (di, dj) with
+        dk = 0, 8 = up, 9 .. 16 the same eight with dk = 1, 17 = down, 18 .. 25 with dk = -1), `converged`, `rounds`, `tile_visits`, `n_bad_seeds`, and
+        `goals` (int32 [S, 4]) and the parameters, for nav_paths3d.  Rounds, max_rounds (None = min(4 * tiles + 64, 65536)), rounds_fixed, check_every
+        and the numpy / torch forms are nav_field's."""
+        if isinstance(cost, dict):
+            cost = cost["cost"]
+        on_dev = hasattr(cost, "is_cuda")
+        if on_dev or device:
+            torch = _torch()
+            dev = torch.device(f"cuda:{self.device}")
+            ct = cost if on_dev else torch.from_numpy(np.ascontiguousarray(np.asarray(cost, dtype=np.uint8)))
+            if ct.dtype != torch.uint8:
+                raise ValueError("nav_field3d: cost must be uint8")
+            ct = ct.to(dev).contiguous()
+            shape = tuple(ct.shape)
+        else:
+            cost = np.asarray(cost)
+            if cost.dtype != np.uint8:
+                raise ValueError("nav_field3d: cost must be uint8")
+            cost = np.ascontiguousarray(cost)
+            shape = cost.shape
+        if len(shape) != 3:
+            raise ValueError("nav_field3d: cost must be [D, H, W]")
+        g = goals.cpu().numpy() if hasattr(goals, "is_cuda") else np.asarray(goals)
+        if g.size == 0:
+            g = np.zeros((0, 4), np.int32)
+        if g.ndim != 2 or g.shape[1] not in (3, 4):
+            raise ValueError("nav_field3d: goals must be [S, 3] or [S, 4]")
+        g4 = np.zeros((g.shape[0], 4), np.int64)
+        g4[:, :g.shape[1]] = g
+        seeds = np.ascontiguousarray((g4 & 0xffffffff).astype(np.uint32).view(np.int32))
+        seeds[:, :3] = np.clip(g4[:, :3], -(1 << 31), (1 << 31) - 1).astype(np.int32)
+        cfg = _lib.NavField3Cfg()
+        cfg.D, cfg.H, cfg.W = shape
+        cfg.neutral, cfg.lethal, cfg.connectivity = int(neutral), int(lethal), int(connectivity)
+        cfg.max_rounds = 0 if max_rounds is None else int(max_rounds)
+        if max_rounds is not None and int(max_rounds) == 0:
+            raise ValueError("nav_field3d: max_rounds must be at least 1")
+        cfg.rounds_fixed = int(rounds_fixed)
+        cfg.check_every = 0 if check_every is None else int(check_every)
+        S = seeds.shape[0]
+        st = _lib.NavField3Stats()
+        if on_dev or device:
+            field = torch.empty(shape, dtype=getattr(torch, "uint32", torch.int32), device=dev)
+            par = torch.empty(shape, dtype=torch.uint8, device=dev) if parent else None
+            sd = torch.from_numpy(seeds).to(dev) if S else None
+            std = torch.zeros(6, dtype=torch.int32, device=dev)
+            ptr = lambda t: None if t is None else t.data_ptr()
+            _lib.check(self.L.tsl_tsdf_nav_field3_dev(self.h, C.byref(cfg), ptr(ct), ptr(sd), S, ptr(field), ptr(par), ptr(std), torch.cuda.current_stream(dev).cuda_stream))
+            sv = std.cpu().numpy()
+            st.converged, st.rounds, st.n_bad_seeds = int(sv[0]), int(sv[1]), int(sv[4])
+            st.tile_visits = int(sv[2:4].view(np.int64)[0])
+        else:
+            field = np.empty(shape, np.uint32)
+            par = np.empty(shape, np.uint8) if parent else None
+            _lib.check(self.L.tsl_tsdf_nav_field3(self.h, C.byref(cfg), _vp(cost), _vp(seeds) if S else None, S, _vp(field), _vp(par), C.byref(st)))
+        out = {"field": field, "converged": int(st.converged), "rounds": int(st.rounds), "tile_visits": int(st.tile_visits), "n_bad_seeds": int(st.n_bad_seeds),
+               "goals": seeds, "neutral": int(neutral), "lethal": int(lethal), "connectivity": int(connectivity)}
+        if par is not None:
+            out["parent"] = par
+        return out
+
+    def nav_paths3d(self, field_result, starts, max_len):
+        """nav_paths in 3-D: the cheapest way to a goal from every start, along the parents of a nav_field3d result (computed with parent=True).
+        starts: [P, 3] = layer, row, col.  Returns a dict: `cells` int16 [P, max_len, 3] = (layer, row, col) from the start on, -1 past the end;
+        `length` int32 [P]; `status` u8 [P] (0 = ended on a goal, 1 = truncated at max_len, 2 = the start is unreached or a wall, 3 = the start is
+        outside); `cost` uint32 [P] = the field at the start.  A result of torch tensors gives tensors, asynchronously on torch.cuda.current_stream
+        (tsl_tsdf_nav_field3_paths_dev); otherwise numpy arrays."""
+        if "parent" not in field_result:
+            raise ValueError("nav_paths3d: the field was computed without parents (nav_field3d(parent=True))")
+        field, par = field_result["field"], field_result["parent"]
+        s = starts.cpu().numpy() if hasattr(starts, "is_cuda") else np.asarray(starts)
+        if s.size == 0:
+            s = np.zeros((0, 3), np.int32)
+        if s.ndim != 2 or s.shape[1] != 3:
+            raise ValueError("nav_paths3d: starts must be [P, 3]")
+        s = np.ascontiguousarray(np.clip(s.astype(np.int64), -(1 << 31), (1 << 31) - 1).astype(np.int32))
+        P, L = s.shape[0], int(max_len)
+        if len(field.shape) != 3:
+            raise ValueError("nav_paths3d: the field must be [D, H, W]")
+        cfg = _lib.NavField3Cfg()
+        cfg.D, cfg.H, cfg.W = tuple(field.shape)
+        Lc = max(L, 0)
+        if hasattr(field, "is_cuda"):
+            torch = _torch()
+            dev = field.device
+            cells = torch.empty((P, Lc, 3), dtype=torch.int16, device=dev)
+            length = torch.empty(P, dtype=torch.int32, device=dev)
+            status = torch.empty(P, dtype=torch.uint8, device=dev)
+            cost = torch.empty(P, dtype=getattr(torch, "uint32", torch.int32), device=dev)
+            sd = torch.from_numpy(s).to(dev) if P else None
+            _lib.check(self.L.tsl_tsdf_nav_field3_paths_dev(self.h, C.byref(cfg), field.data_ptr(), par.data_ptr(), sd.data_ptr() if P else None, P, L, cells.data_ptr(),
+                                                            length.data_ptr(), status.data_ptr(), cost.data_ptr(), torch.cuda.current_stream(dev).cuda_stream))
+        else:
+            field, par = np.ascontiguousarray(field, dtype=np.uint32), np.ascontiguousarray(par, dtype=np.uint8)
+            cells = np.empty((P, Lc, 3), np.int16)
+            length, status, cost = np.empty(P, np.int32), np.empty(P, np.uint8), np.empty(P, np.uint32)
+            _lib.check(self.L.tsl_tsdf_nav_field3_paths(self.h, C.byref(cfg), _vp(field), _vp(par), _vp(s) if P else None, P, L, _vp(cells), _vp(length), _vp(status),
+                                                        _vp(cost)))
+        return {"cells": cells, "length": length, "status": status, "cost": cost}
+
+    def flight_volume(self, stride=4, z_range=None, lut=None, cost_unknown=255, cost_outside=255, refresh=True, device=False):
+        """The cost volume of nav_field3d from the ESDF: a lattice of one sample per cell of `stride`^3 voxels, through query_esdf(interpolate=False)
+        and utils.nav.distance_cost -- no kernel of its own.  Cell (k, i, j) is sampled at the centre of the voxel origin + (k, i, j) * stride +
+        stride // 2 in unsigned voxel coordinates (layer, x, y; unsigned = index + half).  The volume covers the whole map in x and y (N // stride
+        cells) and the layers of z_range = (z0, z1) in metres (default: all), whole cells only.  lut: the u8 [256] table of utils.nav.flight_lut
+        (default: 254 below a quarter voxel, 0 beyond); its `inscribed` must include half a cell diagonal.  Needs an earlier update_esdf; refresh as
+        in query_esdf.  Returns {"cost": u8 [D, H, W], "origin": (k0, i0, j0), "stride", "voxel", "half": (Nz // 2, N // 2, N // 2)}; with
+        device=True the lattice, the query and the cost stay on the map's device and `cost` is a torch tensor, ordered with torch.cuda.current_stream."""
+        from ..utils.nav import distance_cost
+        s = int(stride)
+        if s < 1:
+            raise ValueError("flight_volume: stride must be at least 1")
+        vs = float(self.voxel_scale)
+        uk0, uk1 = 0, self.Nz - 1
+        if z_range is not None:
+            z0, z1 = float(z_range[0]), float(z_range[1])
+            if not (math.isfinite(z0) and math.isfinite(z1)):
+                raise ValueError("flight_volume: z_range is not finite")
+            uk0 = max(uk0, math.ceil(z0 / vs) + self.Nz // 2)
+            uk1 = min(uk1, math.floor(z1 / vs) + self.Nz // 2)
+        D, H, W = (uk1 - uk0 + 1) // s, self.N // s, self.N // s
+        if D < 1 or H < 1:
+            raise ValueError("flight_volume: the range holds no whole cell")
+        if max(D, H, W) > 1024 or D * H * W > (1 << 27):
+            raise ValueError("flight_volume: more than 1024 cells along an axis or 2^27 cells; use a larger stride")
+        if lut is None:
+            lut = np.zeros(256, np.uint8)
+            lut[0] = 254
+        lut = np.ascontiguousarray(np.asarray(lut.cpu().numpy() if hasattr(lut, "cpu") else lut, dtype=np.uint8)).reshape(-1)
+        if lut.shape[0] != 256:
+            raise ValueError("flight_volume: lut must have 256 entries")
+        origin, half = (uk0, 0, 0), (self.Nz // 2, self.N // 2, self.N // 2)
+        # signed voxel index of every sample along each axis, then the lattice in the order [k][i][j] with xyz = (i, j, k) * voxel in float32
+        ax = [np.arange(n, dtype=np.int64) * s + s // 2 + o - h for n, o, h in zip((D, H, W), origin, half)]
+        if device:
+            torch = _torch()
+            dev = torch.device(f"cuda:{self.device}")
+            tk, ti, tj = (torch.from_numpy(a.astype(np.float32)).to(dev) * np.float32(vs).item() for a in ax)
+            xyz = torch.stack([ti[None, :, None].expand(D, H, W), tj[None, None, :].expand(D, H, W), tk[:, None, None].expand(D, H, W)], 3).reshape(-1, 3)
+            dist, _, status = self.query_esdf(xyz, interpolate=False, refresh=refresh)
+            cost = distance_cost(dist, status, vs, lut, cost_unknown, cost_outside).reshape(D, H, W).contiguous()
+        else:
+            fk, fi, fj = (a.astype(np.float32) * np.float32(vs) for a in ax)
+            xyz = np.empty((D, H, W, 3), np.float32)
+            xyz[..., 0], xyz[..., 1], xyz[..., 2] = fi[None, :, None], fj[None, None, :], fk[:, None, None]
+            dist, _, status = self.query_esdf(xyz.reshape(-1, 3), interpolate=False, refresh=refresh)
+            cost = np.ascontiguousarray(distance_cost(dist, status, vs, lut, cost_unknown, cost_outside).reshape(D, H, W))
+        return {"cost": cost, "origin": origin, "stride": s, "voxel": vs, "half": half}
+
     # ---- terrain layers for ground robots (tsl_nav_terrain.hip, DESIGN.md section 4.17) ------------------------------------------
     def nav_terrain(self, bands=None, z_range=None, clearance=1.0, free_run=1, pick="lowest", window=0.2, slope_base=None, max_step=0.1, max_slope_deg=None,
                     min_support=1, radius=1.0, unknown_is_obstacle=False, wall_is_obstacle=False, lut=None, cost_unknown=255, free_thres=None, device=False):

@@ -1,4 +1,5 @@
-"""Helpers around DenseTSDF.nav_grid and DenseTSDF.nav_field (DESIGN.md sections 4.15, 4.16): cost tables for the lookup, the reach of frontier clusters."""
+"""Helpers around DenseTSDF.nav_grid, nav_field and nav_field3d (DESIGN.md sections 4.15, 4.16, 4.18): cost tables for the lookup, the cost of a flight
+volume's cells, the reach of frontier clusters."""
 import numpy as np
 
 
@@ -71,6 +72,83 @@ def frontier_reach(frontiers, field_result, band, N=None, plane=0):
     rows = np.nonzero(ok)[0]
     if rows.size:
         v = f[ui[rows], uj[rows]].astype(np.int64)
+        order = np.lexsort((rows, v, cl[rows]))                  # by cluster, then value, then row
+        first = order[np.concatenate([[True], np.diff(cl[rows][order]) != 0])]
+        hit = v[first] != NAV_UNREACHED
+        value[cl[rows][first][hit]] = v[first][hit].astype(np.uint32)
+        voxel[cl[rows][first][hit]] = rows[first][hit]
+    return {"value": value, "voxel": voxel, "reached": value != NAV_UNREACHED}
+
+
+# ---- 3-D: flight volumes for DenseTSDF.nav_field3d ----------------------------------------------------------------------
+def flight_lut(voxel, inscribed, inflation, scale=10.0):
+    """The u8 [256] cost table of DenseTSDF.flight_volume, indexed by the distance to the nearest surface in quarter voxels, q = floor(4 d / voxel)
+    clipped to 0 .. 255, after the rule of inflation_lut with d = q * voxel / 4 in metres (float64), the near end of the entry's range: 254 (lethal) at
+    q = 0, 253 (inscribed) for 0 < d <= inscribed, floor(252 * exp(-scale * (d - inscribed))) for inscribed < d <= inflation, 0 beyond that.  It never
+    increases with q.  One sample stands for a whole cell of the volume, so `inscribed` must include half a cell diagonal on top of the vehicle's
+    radius: stride * voxel * sqrt(3) / 2 -- a cell whose centre is further than that from every surface holds no surface voxel."""
+    voxel, inscribed, inflation, scale = float(voxel), float(inscribed), float(inflation), float(scale)
+    if not (voxel > 0.0 and inscribed >= 0.0 and inflation >= inscribed and scale >= 0.0 and np.isfinite([voxel, inscribed, inflation, scale]).all()):
+        raise ValueError("flight_lut: needs voxel > 0, 0 <= inscribed <= inflation, scale >= 0, all finite")
+    d = np.arange(256, dtype=np.float64) * (voxel / 4.0)
+    lut = np.floor(252.0 * np.exp(-scale * (d - inscribed)))
+    lut = np.where(d <= inscribed, 253.0, lut)
+    lut = np.where(d > inflation, 0.0, lut)
+    lut[0] = 254.0
+    return lut.astype(np.uint8)
+
+
+def distance_cost(dist, status, voxel, lut, cost_unknown=255, cost_outside=255):
+    """The cost of a cell from the answer of DenseTSDF.query_esdf at its sample: q = clip(floor(float32(dist) * float32(4.0 / voxel)), 0, 255), the
+    distance in quarter voxels, a negative distance (and a NaN) giving 0; status 0 -> lut[q] (u8 [256], flight_lut), 1 (unknown) -> cost_unknown, 2
+    (outside the volume) -> cost_outside; the flag 0x80 of the status is ignored.  Pure: numpy in gives numpy out, torch tensors in give a tensor on
+    their device.  Returns u8 of dist's shape."""
+    k = np.float32(4.0 / float(voxel))
+    if hasattr(dist, "is_cuda"):
+        import torch
+        t = torch.as_tensor(np.asarray(lut, np.uint8).reshape(256), device=dist.device) if not hasattr(lut, "is_cuda") else lut.to(dist.device).reshape(256)
+        q = torch.nan_to_num(torch.floor(dist.float() * float(k)), nan=0.0, posinf=255.0, neginf=0.0).clamp(0.0, 255.0).long()
+        s = status.to(dist.device) & 3
+        c = t[q]
+        c = torch.where(s == 1, torch.full_like(c, int(cost_unknown)), c)
+        return torch.where(s == 2, torch.full_like(c, int(cost_outside)), c)
+    d = np.asarray(dist, np.float32)
+    with np.errstate(invalid="ignore", over="ignore"):
+        q = np.clip(np.nan_to_num(np.floor(d * k), nan=0.0, posinf=255.0, neginf=0.0), 0.0, 255.0).astype(np.int64)
+    s = np.asarray(status, np.uint8) & 3
+    c = np.asarray(lut, np.uint8).reshape(256)[q]
+    c = np.where(s == 1, np.uint8(cost_unknown), c)
+    return np.where(s == 2, np.uint8(cost_outside), c).astype(np.uint8)
+
+
+def frontier_reach3d(frontiers, field_result, volume):
+    """frontier_reach for a DenseTSDF.nav_field3d result: per cluster of a DenseTSDF.extract_frontiers result the least field value over the cells of the
+    flight volume that hold the cluster's voxels, and the voxel that attains it.  volume: the dict of DenseTSDF.flight_volume; the voxel (i, j, k) lies
+    in cell ((k + half[0] - origin[0]) // stride, (i + half[1] - origin[1]) // stride, (j + half[2] - origin[2]) // stride); voxels outside the volume
+    do not count.  Host numpy; tensors are copied.  Returns the dict of frontier_reach: `value` uint32 [m] (NAV_UNREACHED for a cluster that has no voxel
+    in the volume or reaches nothing), `voxel` int64 [m] (the row of frontiers["indices"] that attains it, the first in the frontiers' order on a tie;
+    -1 with NAV_UNREACHED), `reached` bool [m]."""
+    def host(a):
+        return np.asarray(a.cpu().numpy() if hasattr(a, "cpu") else a)
+    f = host(field_result["field"] if isinstance(field_result, dict) else field_result)
+    if f.dtype == np.int32:                                      # a torch build without uint32 hands the bits over as int32
+        f = f.view(np.uint32)
+    if f.ndim != 3:
+        raise ValueError("frontier_reach3d: the field must be [D, H, W]")
+    s = int(volume["stride"])
+    org, half = [int(v) for v in volume["origin"]], [int(v) for v in volume["half"]]
+    idx = host(frontiers["indices"]).astype(np.int64).reshape(-1, 3)
+    cl = host(frontiers["cluster"]).astype(np.int64).reshape(-1)
+    m = len(frontiers["clusters"])
+    value = np.full(m, NAV_UNREACHED, np.uint32)
+    voxel = np.full(m, -1, np.int64)
+    ck = (idx[:, 2] + half[0] - org[0]) // s
+    ci = (idx[:, 0] + half[1] - org[1]) // s
+    cj = (idx[:, 1] + half[2] - org[2]) // s
+    ok = (ck >= 0) & (ck < f.shape[0]) & (ci >= 0) & (ci < f.shape[1]) & (cj >= 0) & (cj < f.shape[2])
+    rows = np.nonzero(ok)[0]
+    if rows.size:
+        v = f[ck[rows], ci[rows], cj[rows]].astype(np.int64)
         order = np.lexsort((rows, v, cl[rows]))                  # by cluster, then value, then row
         first = order[np.concatenate([[True], np.diff(cl[rows][order]) != 0])]
         hit = v[first] != NAV_UNREACHED
