@@ -10,20 +10,18 @@
 //   field[x] = the minimum over move sequences from x to a seed cell of value(seed) + sum of s * (neutral + cost[cell left]), clipped to 2^32 - 2;
 //   TSL_NAV_UNREACHED = 2^32 - 1 where no seed is reached.
 //
-//   k_nf3_seed    one lane per seed: a seed outside or on a wall counts in n_bad; the others atomicMin into the field and mark their tile and its up to 26
-//                 neighbours active.
+// This file holds what is specific to 3-D: the two tuned kernels, the compile-time direction helpers they need and the traits struct Nf3 that describes
+// the solver.  The state, the control block, the clipped add, the seed, finish, seed-parent and paths kernels, the checks, the round loop with the host's
+// check and the bodies of the entry points are in tsl_nav_field_common.hpp, shared with tsl_nav_field.hip.
+//
 //   k_nf3_round   one round = one launch, one workgroup per tile; a tile that is not marked active exits at once.  An active tile loads its field and
 //                 cost with a one-cell halo on all six faces, edges and corners included, into LDS, turns the cost into per-cell registers (5 w, 7 w, 9 w
 //                 and a 26-bit mask of allowed moves, which keeps the corner rule out of the loop) and relaxes in LDS until a block of NF3_BLOCK sweeps
 //                 changes nothing or NF3_SWEEPS is reached (then it marks itself).  Only the owner writes a tile's cells back; a changed cell on a face,
 //                 edge or corner marks EVERY neighbour tile whose halo holds it (up to 7) in the NEXT round's activity map.  Values only fall and each is
 //                 the cost of a real move sequence, so a halo read that races a neighbour's write-back is harmless, as in 2-D.
-//   k_nf3_finish  one lane: the statistics, from the control block.
 //   k_nf3_parent  one lane per cell: the lowest direction code whose neighbour explains the cell's value (codes tried from 25 down).
-//   k_nf3_seed_parent   one lane per seed: parent TSL_NAV3_SEED where the field equals a seed value placed there.
-//   k_nf3_paths   one lane per start: follows parents for at most L cells.
-// No workgroup waits for another, there is no flag to spin on, and every loop has a bound known at launch (NF3_SWEEPS, L).  The host stops the rounds
-// exactly as in tsl_nav_field.hip.
+// No workgroup waits for another, there is no flag to spin on, and every loop has a bound known at launch (NF3_SWEEPS, L).
 //
 // Tile shape and LDS pitch.  A tile is 16 (j) x 8 (i) x 8 (k) = 1024 cells, 4 per lane of a 256-lane workgroup; with the halo 18 x 10 x 10 cells.  A thin
 // tile (32 x 4 x 8 has the same volume and any pitch is conflict-free) was not taken: a round moves information across at most one tile, so the number of
@@ -37,7 +35,7 @@
 // 35.3; on a uniform volume with every tile at work 43.1 / 48.1 / 48.3.  LDS: 10 x 208 words + as many halves = 12.4 KiB; the kernel takes 213 VGPRs, so
 // two workgroups share a CU.  The lane's four cells are four independent chains; the move mask is applied with arithmetic (v | all-ones), not with compare
 // and select, which spilled 119 SGPRs and cost 41.3 us per round.
-#include "tsl_tsdf.hpp"
+#include "tsl_nav_field_common.hpp"
 
 namespace tsl {
 
@@ -51,30 +49,11 @@ namespace tsl {
 #define NF3_LDS (NF3_LDK * NF3_PP)
 #define NF3_SWEEPS 48              // sweeps of a tile per round at most ...
 #define NF3_BLOCK 2                // ... in blocks of this many between two votes (a sweep is 104 reads per lane: the vote is cheap beside it, a quiet block is not)
-#define NF3_MAXV 0xfffffffeu       // the clip of every sum
-#define NF3_MAX_SEEDS 65536
-#define NF3_MAX_STARTS (1 << 20)
-#define NF3_CHECK_DEFAULT 8
 #define NF3_MAX_DIM 1024
 #define NF3_MAX_CELLS (1ll << 27)
 
 static_assert(NF3_PP >= NF3_LDJ * NF3_LDI && NF3_PP % 32 == 16, "the plane pitch must hold a plane and be 16 mod 32 (bank rule of ds_read_b32)");
 static_assert(NF3_TJ * NF3_TI * NF3_TK == 4 * 256, "four cells per lane");
-
-struct Nf3Cfg { int D, H, W, neutral, lethal, nz, tx, ty, tz, max_rounds, rounds_fixed, check_every; };       // nz: non-zero components a move may have (1 .. 3)
-
-struct Nf3Ctl { uint32_t marks[2]; int32_t rounds, n_bad; unsigned long long visits; };
-
-struct NavField3State {
-    void *cost, *seeds, *field, *parent, *act, *ctl, *stats, *starts, *cells, *plen, *pstatus, *pcost;
-    size_t b_cost, b_seeds, b_field, b_parent, b_act, b_ctl, b_stats, b_starts, b_cells, b_plen, b_pstatus, b_pcost;
-    uint32_t* pin;                 // pinned: the count the host reads between rounds, and the statistics on their way back
-};
-
-__device__ __forceinline__ uint32_t nf3_add(uint32_t a, uint32_t c)     // a + c clipped to NF3_MAXV; unreached stays unreached
-{
-    return a == TSL_NAV_UNREACHED ? a : (a > NF3_MAXV - c ? NF3_MAXV : a + c);
-}
 
 // direction code -> (dk, di, dj); constant-folded where the code is a constant of an unrolled loop
 __host__ __device__ constexpr int nf3_e(int d) { return d < 8 ? d : (d < 17 ? d - 9 : d - 18); }            // the 2-D code, -1 for the two vertical moves
@@ -98,31 +77,9 @@ __constant__ int c_nf3_dk[26] = { 0, 0, 0, 0, 0, 0, 0, 0, 1, 1, 1, 1, 1, 1, 1, 1
 __constant__ int c_nf3_di[26] = { 1, 1, 0, -1, -1, -1, 0, 1, 0, 1, 1, 0, -1, -1, -1, 0, 1, 0, 1, 1, 0, -1, -1, -1, 0, 1 };
 __constant__ int c_nf3_dj[26] = { 0, 1, 1, 1, 0, -1, -1, -1, 0, 0, 1, 1, 1, 0, -1, -1, -1, 0, 0, 1, 1, 1, 0, -1, -1, -1 };
 
-// ---- seeds -----------------------------------------------------------------------------------------------------------------------------------
-__global__ void __launch_bounds__(256) k_nf3_seed(Nf3Cfg C, const uint8_t* __restrict__ cost, const int32_t* __restrict__ seeds, int S, uint32_t* field, uint32_t* act,
-                                                  Nf3Ctl* ctl)
-{
-    const int s = (int)(blockIdx.x * 256 + threadIdx.x);
-    if (s >= S) return;
-    const int k = seeds[s * 4], r = seeds[s * 4 + 1], c = seeds[s * 4 + 2];
-    const uint32_t v = (uint32_t)seeds[s * 4 + 3];
-    bool ok = k >= 0 && k < C.D && r >= 0 && r < C.H && c >= 0 && c < C.W;
-    size_t o = 0;
-    if (ok) { o = ((size_t)k * C.H + r) * C.W + c; ok = (int)cost[o] < C.lethal; }
-    if (!ok) { atomicAdd(&ctl->n_bad, 1); return; }
-    atomicMin(&field[o], v > NF3_MAXV ? NF3_MAXV : v);
-    const int tk = k / NF3_TK, tr = r / NF3_TI, tc = c / NF3_TJ;
-    for (int a = -1; a <= 1; ++a)
-        for (int b = -1; b <= 1; ++b)
-            for (int e = -1; e <= 1; ++e) {
-                const int nk = tk + a, nr = tr + b, nc = tc + e;
-                if (nk >= 0 && nk < C.tz && nr >= 0 && nr < C.ty && nc >= 0 && nc < C.tx) act[((size_t)nk * C.ty + nr) * C.tx + nc] = 1u;
-            }
-}
-
 // ---- one round -------------------------------------------------------------------------------------------------------------------------------
 // grid (tx, ty, tz).  act_cur: this round's activity map (a tile clears its own word), act_next: the next round's.  parity = round & 1.
-__global__ void __launch_bounds__(256) k_nf3_round(Nf3Cfg C, const uint8_t* __restrict__ cost, uint32_t* field, uint32_t* act_cur, uint32_t* act_next, Nf3Ctl* ctl,
+__global__ void __launch_bounds__(256) k_nf3_round(NfCfg C, const uint8_t* __restrict__ cost, uint32_t* field, uint32_t* act_cur, uint32_t* act_next, NfCtl* ctl,
                                                    int round)
 {
     __shared__ uint32_t sf[NF3_LDS];
@@ -205,7 +162,7 @@ __global__ void __launch_bounds__(256) k_nf3_round(Nf3Cfg C, const uint8_t* __re
             }
 #pragma unroll
             for (int c = 0; c < 4; ++c) {
-                const uint32_t cand = min(nf3_add(m5[c], w5[c]), min(nf3_add(m7[c], w7[c]), nf3_add(m9[c], w9[c])));
+                const uint32_t cand = min(nf_add(m5[c], w5[c]), min(nf_add(m7[c], w7[c]), nf_add(m9[c], w9[c])));
                 if (mask[c] && cand < f[c]) { f[c] = cand; sf[idx[c]] = cand; ch = true; }
             }
             __asm__ volatile("" ::: "memory");
@@ -249,18 +206,8 @@ __global__ void __launch_bounds__(256) k_nf3_round(Nf3Cfg C, const uint8_t* __re
     atomicMax(&ctl->rounds, round + 1);
 }
 
-__global__ void k_nf3_finish(const Nf3Ctl* __restrict__ ctl, int last_round, tsl_nav_field3_stats* st)
-{
-    if (threadIdx.x != 0 || blockIdx.x != 0) return;
-    st->converged = ctl->marks[last_round & 1] == 0u ? 1 : 0;
-    st->rounds = ctl->rounds;
-    st->tile_visits = (int64_t)ctl->visits;
-    st->n_bad_seeds = ctl->n_bad;
-    st->reserved_ = 0;
-}
-
 // ---- parents ---------------------------------------------------------------------------------------------------------------------------------
-__global__ void __launch_bounds__(256) k_nf3_parent(Nf3Cfg C, const uint8_t* __restrict__ cost, const uint32_t* __restrict__ field, uint8_t* __restrict__ parent)
+__global__ void __launch_bounds__(256) k_nf3_parent(NfCfg C, const uint8_t* __restrict__ cost, const uint32_t* __restrict__ field, uint8_t* __restrict__ parent)
 {
     const size_t o = (size_t)blockIdx.x * 256 + threadIdx.x;
     const size_t hw = (size_t)C.H * C.W;
@@ -286,186 +233,49 @@ __global__ void __launch_bounds__(256) k_nf3_parent(Nf3Cfg C, const uint8_t* __r
         for (int d = 25; d >= 0; --d) {                             // downwards: the lowest code that explains f is the one that stays
             if (nf3_nz(d) > C.nz || (open & nf3_need(d)) != nf3_need(d)) continue;
             const uint32_t fn = field[(size_t)(k + nf3_dk(d)) * hw + (size_t)(r + nf3_di(d)) * C.W + c + nf3_dj(d)];
-            if (fn != TSL_NAV_UNREACHED && nf3_add(fn, (nf3_nz(d) == 1 ? 5u : (nf3_nz(d) == 2 ? 7u : 9u)) * w) == f) par = (uint32_t)d;
+            if (fn != TSL_NAV_UNREACHED && nf_add(fn, (nf3_nz(d) == 1 ? 5u : (nf3_nz(d) == 2 ? 7u : 9u)) * w) == f) par = (uint32_t)d;
         }
     }
     parent[o] = (uint8_t)par;
 }
 
-__global__ void __launch_bounds__(256) k_nf3_seed_parent(Nf3Cfg C, const uint8_t* __restrict__ cost, const int32_t* __restrict__ seeds, int S,
-                                                         const uint32_t* __restrict__ field, uint8_t* parent)
-{
-    const int s = (int)(blockIdx.x * 256 + threadIdx.x);
-    if (s >= S) return;
-    const int k = seeds[s * 4], r = seeds[s * 4 + 1], c = seeds[s * 4 + 2];
-    const uint32_t v = (uint32_t)seeds[s * 4 + 3];
-    if (!(k >= 0 && k < C.D && r >= 0 && r < C.H && c >= 0 && c < C.W)) return;
-    const size_t o = ((size_t)k * C.H + r) * C.W + c;
-    if ((int)cost[o] >= C.lethal) return;
-    if (field[o] == (v > NF3_MAXV ? NF3_MAXV : v)) parent[o] = TSL_NAV3_SEED;      // (several seeds of one value on a cell store the same byte)
-}
-
-// ---- paths -----------------------------------------------------------------------------------------------------------------------------------
-__global__ void __launch_bounds__(64) k_nf3_paths(int D, int H, int W, const uint32_t* __restrict__ field, const uint8_t* __restrict__ parent,
-                                                  const int32_t* __restrict__ starts, int P, int L, int16_t* __restrict__ cells, int32_t* __restrict__ length,
-                                                  uint8_t* __restrict__ status, uint32_t* __restrict__ cost)
-{
-    const int q = (int)(blockIdx.x * 64 + threadIdx.x);
-    if (q >= P) return;
-    int k = starts[q * 3], r = starts[q * 3 + 1], c = starts[q * 3 + 2];
-    int st = 1, len = 0;                                            // truncated unless the walk ends
-    uint32_t f = TSL_NAV_UNREACHED;
-    bool go = true;
-    const size_t hw = (size_t)H * W;
-    if (!(k >= 0 && k < D && r >= 0 && r < H && c >= 0 && c < W)) { st = 3; go = false; }
-    else {
-        const size_t o = (size_t)k * hw + (size_t)r * W + c;
-        f = field[o];
-        if (f == TSL_NAV_UNREACHED || parent[o] > TSL_NAV3_SEED) { st = 2; go = false; }
+// ---- the solver, as tsl_nav_field_common.hpp sees it -----------------------------------------------------------------------------------------
+struct Nf3 {
+    static constexpr int TX = NF3_TJ, TY = NF3_TI, TZ = NF3_TK, SEED = TSL_NAV3_SEED, NCOMP = 3;
+    static constexpr bool LINKED = true;                            // the leading axis is the layers of one volume
+    typedef tsl_nav_field3_cfg cfg_t;
+    typedef tsl_nav_field3_stats stats_t;
+    static constexpr const char* name = "nav_field3";
+    static constexpr const char* conn_text = ": connectivity must be 6, 18 or 26";
+    static constexpr int K_SEED = -1, K_ROUND = -1, K_PARENT = -1, K_PATHS = -1;      // no profiling id: time the _dev call with events
+    static NavFieldState*& state(tsl_tsdf* m) { return m->nav_field3; }
+    static int dims(const cfg_t* c, const std::string& w, NfCfg* C)
+    {
+        TSL_REQUIRE(c->D >= 1 && c->D <= NF3_MAX_DIM, w + ": D must be 1 .. 1024");
+        TSL_REQUIRE(c->H >= 1 && c->H <= NF3_MAX_DIM, w + ": H must be 1 .. 1024");
+        TSL_REQUIRE(c->W >= 1 && c->W <= NF3_MAX_DIM, w + ": W must be 1 .. 1024");
+        TSL_REQUIRE((long long)c->D * c->H * c->W <= NF3_MAX_CELLS, w + ": D * H * W is above 2^27 cells");
+        C->D = c->D; C->H = c->H; C->W = c->W;
+        return TSL_OK;
     }
-    int16_t* out = cells ? cells + (size_t)q * L * 3 : nullptr;
-    for (int t = 0; t < L; ++t) {
-        int16_t a = -1, b = -1, e = -1;
-        if (go) {
-            a = (int16_t)k; b = (int16_t)r; e = (int16_t)c; len = t + 1;
-            const int par = parent[(size_t)k * hw + (size_t)r * W + c];
-            if (par == TSL_NAV3_SEED) { st = 0; go = false; }
-            else if (par > TSL_NAV3_SEED) { st = 2; go = false; }   // a parent volume that is not of this field
-            else {
-                k += c_nf3_dk[par]; r += c_nf3_di[par]; c += c_nf3_dj[par];
-                if (!(k >= 0 && k < D && r >= 0 && r < H && c >= 0 && c < W)) { st = 2; go = false; }
-            }
-        }
-        if (out) { out[t * 3] = a; out[t * 3 + 1] = b; out[t * 3 + 2] = e; }
+    static int rank(int conn) { return conn == 6 ? 1 : (conn == 18 ? 2 : (conn == 26 ? 3 : 0)); }
+    static int default_rounds(const NfCfg& C)
+    {
+        const long long cap = 4ll * C.tx * C.ty * C.tz + 64;
+        return (int)(cap < 65536 ? cap : 65536);
     }
-    if (length) length[q] = len;
-    if (status) status[q] = (uint8_t)st;
-    if (cost) cost[q] = f;
-}
-
-// ---- host ------------------------------------------------------------------------------------------------------------------------------------
-void nav_field3_release(tsl_tsdf* m)
-{
-    NavField3State* S = m->nav_field3;
-    if (!S) return;
-    void* ptrs[] = { S->cost, S->seeds, S->field, S->parent, S->act, S->ctl, S->stats, S->starts, S->cells, S->plen, S->pstatus, S->pcost };
-    for (void* p : ptrs) if (p) (void)hipFree(p);
-    if (S->pin) (void)hipHostFree(S->pin);
-    delete S;
-    m->nav_field3 = nullptr;
-}
-
-static int nf3_dims(const tsl_nav_field3_cfg* c, const std::string& w)
-{
-    TSL_REQUIRE(c->D >= 1 && c->D <= NF3_MAX_DIM, w + ": D must be 1 .. 1024");
-    TSL_REQUIRE(c->H >= 1 && c->H <= NF3_MAX_DIM, w + ": H must be 1 .. 1024");
-    TSL_REQUIRE(c->W >= 1 && c->W <= NF3_MAX_DIM, w + ": W must be 1 .. 1024");
-    TSL_REQUIRE((long long)c->D * c->H * c->W <= NF3_MAX_CELLS, w + ": D * H * W is above 2^27 cells");
-    return TSL_OK;
-}
-
-static int nf3_check(tsl_tsdf* m, const tsl_nav_field3_cfg* c, const void* cost, const void* seeds, int S, const void* field, Nf3Cfg* C, const char* who)
-{
-    const std::string w(who);
-    TSL_REQUIRE(m, w + ": null handle");
-    TSL_REQUIRE(c, w + ": null cfg");
-    TSL_REQUIRE(cost, w + ": null cost");
-    TSL_REQUIRE(field, w + ": null field");
-    int rc = nf3_dims(c, w); if (rc) return rc;
-    TSL_REQUIRE(S >= 0 && S <= NF3_MAX_SEEDS, w + ": S must be 0 .. 65536 seeds");
-    TSL_REQUIRE(seeds || S == 0, w + ": null seeds while S > 0");
-    TSL_REQUIRE(c->neutral >= 1 && c->neutral <= 255, w + ": neutral must be 1 .. 255");
-    TSL_REQUIRE(c->lethal >= 1 && c->lethal <= 255, w + ": lethal must be 1 .. 255");
-    TSL_REQUIRE(c->connectivity == 6 || c->connectivity == 18 || c->connectivity == 26, w + ": connectivity must be 6, 18 or 26");
-    TSL_REQUIRE(c->max_rounds >= 0, w + ": max_rounds is negative");
-    TSL_REQUIRE(c->rounds_fixed >= 0, w + ": rounds_fixed is negative");
-    TSL_REQUIRE(c->check_every >= 0, w + ": check_every is negative");
-    C->D = c->D; C->H = c->H; C->W = c->W; C->neutral = c->neutral; C->lethal = c->lethal;
-    C->nz = c->connectivity == 6 ? 1 : (c->connectivity == 18 ? 2 : 3);
-    C->tx = (c->W + NF3_TJ - 1) / NF3_TJ; C->ty = (c->H + NF3_TI - 1) / NF3_TI; C->tz = (c->D + NF3_TK - 1) / NF3_TK;
-    const long long cap = 4ll * C->tx * C->ty * C->tz + 64;
-    C->max_rounds = c->max_rounds ? c->max_rounds : (int)(cap < 65536 ? cap : 65536);
-    C->rounds_fixed = c->rounds_fixed;
-    C->check_every = c->check_every ? c->check_every : NF3_CHECK_DEFAULT;
-    return TSL_OK;
-}
-
-#define NF3_GROW(field, bytes_field, bytes) do { if ((rc = grow(&S->field, &S->bytes_field, (bytes)))) return rc; } while (0)
-
-static int nf3_state(tsl_tsdf* m)
-{
-    if (m->nav_field3) return TSL_OK;
-    NavField3State* S = new NavField3State();                       // value-initialised: every pointer null, every size 0
-    if (hipHostMalloc((void**)&S->pin, 64) != hipSuccess) { delete S; (void)hipGetLastError(); set_error("nav_field3: no pinned memory"); return TSL_ERR_HIP; }
-    m->nav_field3 = S;
-    return TSL_OK;
-}
-
-// everything on q, every pointer a device pointer.  With rounds_fixed = 0 it waits for q at each check.
-static int nf3_launch(tsl_tsdf* m, hipStream_t q, const Nf3Cfg& C, const uint8_t* cost, const int32_t* seeds, int S_n, uint32_t* field, uint8_t* parent,
-                      tsl_nav_field3_stats* stats)
-{
-    int rc;
-    NavField3State* S = m->nav_field3;
-    const size_t tiles = (size_t)C.tx * C.ty * C.tz, cells = (size_t)C.D * C.H * C.W;
-    NF3_GROW(act, b_act, tiles * 2 * sizeof(uint32_t));
-    NF3_GROW(ctl, b_ctl, sizeof(Nf3Ctl));
-    NF3_GROW(stats, b_stats, sizeof(tsl_nav_field3_stats));
-    if (!stats) stats = (tsl_nav_field3_stats*)S->stats;
-    uint32_t* act = (uint32_t*)S->act;
-    Nf3Ctl* ctl = (Nf3Ctl*)S->ctl;
-    TSL_HIP(hipMemsetAsync(field, 0xff, cells * sizeof(uint32_t), q));
-    TSL_HIP(hipMemsetAsync(act, 0, tiles * 2 * sizeof(uint32_t), q));
-    TSL_HIP(hipMemsetAsync(ctl, 0, sizeof(Nf3Ctl), q));
-    if (S_n > 0) {
-        hipLaunchKernelGGL(k_nf3_seed, dim3((unsigned)((S_n + 255) / 256)), dim3(256), 0, q, C, cost, seeds, S_n, field, act, ctl);
-        TSL_HIP(hipGetLastError());
+    __device__ static void step(int code, int& k, int& r, int& c) { k += c_nf3_dk[code]; r += c_nf3_di[code]; c += c_nf3_dj[code]; }
+    static void round(hipStream_t q, const NfCfg& C, const uint8_t* cost, uint32_t* field, uint32_t* act_cur, uint32_t* act_next, NfCtl* ctl, int r)
+    {
+        hipLaunchKernelGGL(k_nf3_round, dim3((unsigned)C.tx, (unsigned)C.ty, (unsigned)C.tz), dim3(256), 0, q, C, cost, field, act_cur, act_next, ctl, r);
     }
-    const dim3 grid((unsigned)C.tx, (unsigned)C.ty, (unsigned)C.tz);
-    int r = 0;
-    const int total = C.rounds_fixed > 0 ? C.rounds_fixed : C.max_rounds;
-    while (r < total) {
-        const int n = C.rounds_fixed > 0 ? total : (C.check_every < total - r ? C.check_every : total - r);
-        for (int e = r + n; r < e; ++r)
-            hipLaunchKernelGGL(k_nf3_round, grid, dim3(256), 0, q, C, cost, field, act + (size_t)(r & 1) * tiles, act + (size_t)((r & 1) ^ 1) * tiles, ctl, r);
-        TSL_HIP(hipGetLastError());
-        if (C.rounds_fixed > 0) break;
-        TSL_HIP(hipMemcpyAsync(S->pin, &ctl->marks[(r - 1) & 1], sizeof(uint32_t), hipMemcpyDeviceToHost, q));
-        TSL_HIP(hipStreamSynchronize(q));
-        if (S->pin[0] == 0u) break;                                 // the last round marked nothing: nothing is active
+    static void parent(hipStream_t q, const NfCfg& C, const uint8_t* cost, const uint32_t* field, uint8_t* par)
+    {
+        hipLaunchKernelGGL(k_nf3_parent, dim3((unsigned)(((size_t)C.D * C.H * C.W + 255) / 256)), dim3(256), 0, q, C, cost, field, par);
     }
-    hipLaunchKernelGGL(k_nf3_finish, dim3(1), dim3(64), 0, q, ctl, r - 1, stats);
-    if (parent) {
-        hipLaunchKernelGGL(k_nf3_parent, dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, q, C, cost, field, parent);
-        if (S_n > 0) hipLaunchKernelGGL(k_nf3_seed_parent, dim3((unsigned)((S_n + 255) / 256)), dim3(256), 0, q, C, cost, seeds, S_n, field, parent);
-    }
-    TSL_HIP(hipGetLastError());
-    return TSL_OK;
-}
+};
 
-static int nf3_paths_check(tsl_tsdf* m, const tsl_nav_field3_cfg* c, const void* field, const void* parent, const void* starts, int P, int L, const char* who)
-{
-    const std::string w(who);
-    TSL_REQUIRE(m, w + ": null handle");
-    TSL_REQUIRE(c, w + ": null cfg");
-    TSL_REQUIRE(field, w + ": null field");
-    TSL_REQUIRE(parent, w + ": null parent");
-    int rc = nf3_dims(c, w); if (rc) return rc;
-    TSL_REQUIRE(P >= 0 && P <= NF3_MAX_STARTS, w + ": P must be 0 .. 2^20 starts");
-    TSL_REQUIRE(starts || P == 0, w + ": null starts while P > 0");
-    TSL_REQUIRE(L >= 1, w + ": L must be at least 1");
-    TSL_REQUIRE((long long)P * L <= (1ll << 28), w + ": P * L is above 2^28 cells");
-    return TSL_OK;
-}
-
-static int nf3_paths_launch(hipStream_t q, const tsl_nav_field3_cfg* c, const uint32_t* field, const uint8_t* parent, const int32_t* starts, int P, int L,
-                            int16_t* cells, int32_t* length, uint8_t* status, uint32_t* cost)
-{
-    if (P == 0) return TSL_OK;
-    hipLaunchKernelGGL(k_nf3_paths, dim3((unsigned)((P + 63) / 64)), dim3(64), 0, q, c->D, c->H, c->W, field, parent, starts, P, L, cells, length, status, cost);
-    TSL_HIP(hipGetLastError());
-    return TSL_OK;
-}
+void nav_field3_release(tsl_tsdf* m) { nf_release(&m->nav_field3); }
 
 }  // namespace tsl
 
@@ -476,85 +286,25 @@ extern "C" {
 int tsl_tsdf_nav_field3(tsl_tsdf* m, const tsl_nav_field3_cfg* cfg, const uint8_t* cost, const int32_t* seeds, int32_t n_seeds, uint32_t* field, uint8_t* parent,
                         tsl_nav_field3_stats* stats)
 {
-    Nf3Cfg C;
-    int rc = nf3_check(m, cfg, cost, seeds, n_seeds, field, &C, "nav_field3"); if (rc) return rc;
-    TSL_HIP(hipSetDevice(m->device));
-    const hipStream_t q = ms(m);
-    if ((rc = nf3_state(m))) return rc;
-    NavField3State* S = m->nav_field3;
-    const size_t cells = (size_t)C.D * C.H * C.W;
-    NF3_GROW(cost, b_cost, cells);
-    NF3_GROW(field, b_field, cells * sizeof(uint32_t));
-    if (parent) NF3_GROW(parent, b_parent, cells);
-    if (n_seeds > 0) NF3_GROW(seeds, b_seeds, (size_t)n_seeds * 4 * sizeof(int32_t));
-    NF3_GROW(stats, b_stats, sizeof(tsl_nav_field3_stats));
-    TSL_HIP(hipMemcpyAsync(S->cost, cost, cells, hipMemcpyHostToDevice, q));
-    if (n_seeds > 0) TSL_HIP(hipMemcpyAsync(S->seeds, seeds, (size_t)n_seeds * 4 * sizeof(int32_t), hipMemcpyHostToDevice, q));
-    if ((rc = nf3_launch(m, q, C, (const uint8_t*)S->cost, (const int32_t*)S->seeds, n_seeds, (uint32_t*)S->field, parent ? (uint8_t*)S->parent : nullptr,
-                         (tsl_nav_field3_stats*)S->stats))) return rc;
-    TSL_HIP(hipMemcpyAsync(S->pin + 4, S->stats, sizeof(tsl_nav_field3_stats), hipMemcpyDeviceToHost, q));
-    TSL_HIP(hipStreamSynchronize(q));
-    TSL_HIP(hipMemcpy(field, S->field, cells * sizeof(uint32_t), hipMemcpyDeviceToHost));
-    if (parent) TSL_HIP(hipMemcpy(parent, S->parent, cells, hipMemcpyDeviceToHost));
-    if (stats) memcpy(stats, S->pin + 4, sizeof(tsl_nav_field3_stats));
-    return TSL_OK;
+    return nf_field_host<Nf3>(m, cfg, cost, seeds, n_seeds, field, parent, stats);
 }
 
 int tsl_tsdf_nav_field3_dev(tsl_tsdf* m, const tsl_nav_field3_cfg* cfg, const void* cost_dev, const void* seeds_dev, int32_t n_seeds, void* field_dev, void* parent_dev,
                             void* stats_dev, void* user_stream)
 {
-    Nf3Cfg C;
-    int rc = nf3_check(m, cfg, cost_dev, seeds_dev, n_seeds, field_dev, &C, "nav_field3_dev"); if (rc) return rc;
-    TSL_HIP(hipSetDevice(m->device));
-    const hipStream_t q = ms(m);
-    if ((rc = nf3_state(m))) return rc;
-    if ((rc = order_before(m, (hipStream_t)user_stream, q))) return rc;
-    if ((rc = nf3_launch(m, q, C, (const uint8_t*)cost_dev, (const int32_t*)seeds_dev, n_seeds, (uint32_t*)field_dev, (uint8_t*)parent_dev,
-                         (tsl_nav_field3_stats*)stats_dev))) return rc;
-    return order_after(m, (hipStream_t)user_stream, q);
+    return nf_field_dev<Nf3>(m, cfg, cost_dev, seeds_dev, n_seeds, field_dev, parent_dev, stats_dev, user_stream);
 }
 
 int tsl_tsdf_nav_field3_paths(tsl_tsdf* m, const tsl_nav_field3_cfg* cfg, const uint32_t* field, const uint8_t* parent, const int32_t* starts, int32_t n_starts,
                               int32_t max_len, int16_t* cells, int32_t* length, uint8_t* status, uint32_t* cost)
 {
-    int rc = nf3_paths_check(m, cfg, field, parent, starts, n_starts, max_len, "nav_field3_paths"); if (rc) return rc;
-    if (n_starts == 0) return TSL_OK;
-    TSL_HIP(hipSetDevice(m->device));
-    const hipStream_t q = ms(m);
-    if ((rc = nf3_state(m))) return rc;
-    NavField3State* S = m->nav_field3;
-    const size_t ncells = (size_t)cfg->D * cfg->H * cfg->W, P = (size_t)n_starts, L = (size_t)max_len;
-    NF3_GROW(field, b_field, ncells * sizeof(uint32_t));
-    NF3_GROW(parent, b_parent, ncells);
-    NF3_GROW(starts, b_starts, P * 3 * sizeof(int32_t));
-    NF3_GROW(cells, b_cells, P * L * 3 * sizeof(int16_t));
-    NF3_GROW(plen, b_plen, P * sizeof(int32_t));
-    NF3_GROW(pstatus, b_pstatus, P);
-    NF3_GROW(pcost, b_pcost, P * sizeof(uint32_t));
-    TSL_HIP(hipMemcpyAsync(S->field, field, ncells * sizeof(uint32_t), hipMemcpyHostToDevice, q));
-    TSL_HIP(hipMemcpyAsync(S->parent, parent, ncells, hipMemcpyHostToDevice, q));
-    TSL_HIP(hipMemcpyAsync(S->starts, starts, P * 3 * sizeof(int32_t), hipMemcpyHostToDevice, q));
-    if ((rc = nf3_paths_launch(q, cfg, (const uint32_t*)S->field, (const uint8_t*)S->parent, (const int32_t*)S->starts, n_starts, max_len, (int16_t*)S->cells,
-                               (int32_t*)S->plen, (uint8_t*)S->pstatus, (uint32_t*)S->pcost))) return rc;
-    TSL_HIP(hipStreamSynchronize(q));
-    if (cells) TSL_HIP(hipMemcpy(cells, S->cells, P * L * 3 * sizeof(int16_t), hipMemcpyDeviceToHost));
-    if (length) TSL_HIP(hipMemcpy(length, S->plen, P * sizeof(int32_t), hipMemcpyDeviceToHost));
-    if (status) TSL_HIP(hipMemcpy(status, S->pstatus, P, hipMemcpyDeviceToHost));
-    if (cost) TSL_HIP(hipMemcpy(cost, S->pcost, P * sizeof(uint32_t), hipMemcpyDeviceToHost));
-    return TSL_OK;
+    return nf_paths_host<Nf3>(m, cfg, field, parent, starts, n_starts, max_len, cells, length, status, cost);
 }
 
 int tsl_tsdf_nav_field3_paths_dev(tsl_tsdf* m, const tsl_nav_field3_cfg* cfg, const void* field_dev, const void* parent_dev, const void* starts_dev, int32_t n_starts,
                                   int32_t max_len, void* cells_dev, void* length_dev, void* status_dev, void* cost_dev, void* user_stream)
 {
-    int rc = nf3_paths_check(m, cfg, field_dev, parent_dev, starts_dev, n_starts, max_len, "nav_field3_paths_dev"); if (rc) return rc;
-    if (n_starts == 0) return TSL_OK;
-    TSL_HIP(hipSetDevice(m->device));
-    const hipStream_t q = ms(m);
-    if ((rc = order_before(m, (hipStream_t)user_stream, q))) return rc;
-    if ((rc = nf3_paths_launch(q, cfg, (const uint32_t*)field_dev, (const uint8_t*)parent_dev, (const int32_t*)starts_dev, n_starts, max_len, (int16_t*)cells_dev,
-                               (int32_t*)length_dev, (uint8_t*)status_dev, (uint32_t*)cost_dev))) return rc;
-    return order_after(m, (hipStream_t)user_stream, q);
+    return nf_paths_dev<Nf3>(m, cfg, field_dev, parent_dev, starts_dev, n_starts, max_len, cells_dev, length_dev, status_dev, cost_dev, user_stream);
 }
 
 }  // extern "C"

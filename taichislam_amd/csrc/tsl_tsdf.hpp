@@ -228,12 +228,11 @@ struct MeshIdxState;                     // tsl_mesh_indexed.hip: scratch and bu
 void mesh_indexed_release(tsl_tsdf* m);
 struct NavState;                         // tsl_nav_grid.hip: scratch and host staging of the navigation grids (allocated by the first call)
 void nav_release(tsl_tsdf* m);
-struct NavFieldState;                    // tsl_nav_field.hip: scratch, control block and pinned words of the cost-to-go fields (allocated by the first call)
-void nav_field_release(tsl_tsdf* m);
+struct NavFieldState;                    // tsl_nav_field_common.hpp: scratch, control block and pinned words of a cost-to-go solver (allocated by its first call)
+void nav_field_release(tsl_tsdf* m);     // tsl_nav_field.hip: the 2-D solver's instance
 struct NavTerrainState;                  // tsl_nav_terrain.hip: scratch and host staging of the terrain layers (allocated by the first call)
 void nav_terrain_release(tsl_tsdf* m);
-struct NavField3State;                   // tsl_nav_field3.hip: scratch, control block and pinned words of the 3-D cost-to-go fields (allocated by the first call)
-void nav_field3_release(tsl_tsdf* m);
+void nav_field3_release(tsl_tsdf* m);    // tsl_nav_field3.hip: the 3-D solver's instance
 }  // namespace tsl
 
 #define TSL_ESDF_SLOTS 4
@@ -309,7 +308,7 @@ struct tsl_tsdf {
     tsl::NavState* nav;                  // tsl_nav_grid.hip (allocated by the first call)
     tsl::NavFieldState* nav_field;       // tsl_nav_field.hip (allocated by the first call)
     tsl::NavTerrainState* nav_terrain;   // tsl_nav_terrain.hip (allocated by the first call)
-    tsl::NavField3State* nav_field3;     // tsl_nav_field3.hip (allocated by the first call)
+    tsl::NavFieldState* nav_field3;      // tsl_nav_field3.hip (allocated by the first call)
 };
 
 namespace tsl {

@@ -1090,6 +1090,104 @@ class DenseTSDF(BaseMap):
                 out[k] = v
         return out
 
+    # ---- cost-to-go fields and paths: the one body of nav_field / nav_field3d and of nav_paths / nav_paths3d ----------------------
+    def _nav_field_call(self, who, shape_rule, shape_text, cfg_cls, stats_cls, fn_host, fn_dev, cost, goals, neutral, lethal, connectivity, parent, max_rounds,
+                        rounds_fixed, check_every, device):
+        """who: the name in messages; shape_rule: the cost's shape -> the three extents, or None for one that is refused with shape_text; cfg_cls,
+        stats_cls: the ctypes forms of the entry points fn_host (numpy) and fn_dev (torch)."""
+        if isinstance(cost, dict):
+            cost = cost["cost"]
+        on_dev = hasattr(cost, "is_cuda")
+        if on_dev or device:
+            torch = _torch()
+            dev = torch.device(f"cuda:{self.device}")
+            ct = cost if on_dev else torch.from_numpy(np.ascontiguousarray(np.asarray(cost, dtype=np.uint8)))
+            if ct.dtype != torch.uint8:
+                raise ValueError(f"{who}: cost must be uint8")
+            ct = ct.to(dev).contiguous()
+            shape = tuple(ct.shape)
+        else:
+            cost = np.asarray(cost)
+            if cost.dtype != np.uint8:
+                raise ValueError(f"{who}: cost must be uint8")
+            cost = np.ascontiguousarray(cost)
+            shape = tuple(cost.shape)
+        shape = shape_rule(shape)
+        if shape is None:
+            raise ValueError(f"{who}: cost must be {shape_text}")
+        g = goals.cpu().numpy() if hasattr(goals, "is_cuda") else np.asarray(goals)
+        if g.size == 0:
+            g = np.zeros((0, 4), np.int32)
+        if g.ndim != 2 or g.shape[1] not in (3, 4):
+            raise ValueError(f"{who}: goals must be [S, 3] or [S, 4]")
+        g4 = np.zeros((g.shape[0], 4), np.int64)
+        g4[:, :g.shape[1]] = g
+        seeds = np.ascontiguousarray((g4 & 0xffffffff).astype(np.uint32).view(np.int32))
+        seeds[:, :3] = np.clip(g4[:, :3], -(1 << 31), (1 << 31) - 1).astype(np.int32)
+        cfg = cfg_cls(*shape)                                       # the three extents lead both structs
+        cfg.neutral, cfg.lethal, cfg.connectivity = int(neutral), int(lethal), int(connectivity)
+        cfg.max_rounds = 0 if max_rounds is None else int(max_rounds)
+        if max_rounds is not None and int(max_rounds) == 0:
+            raise ValueError(f"{who}: max_rounds must be at least 1")
+        cfg.rounds_fixed = int(rounds_fixed)
+        cfg.check_every = 0 if check_every is None else int(check_every)
+        S = seeds.shape[0]
+        st = stats_cls()
+        if on_dev or device:
+            field = torch.empty(shape, dtype=getattr(torch, "uint32", torch.int32), device=dev)
+            par = torch.empty(shape, dtype=torch.uint8, device=dev) if parent else None
+            sd = torch.from_numpy(seeds).to(dev) if S else None
+            std = torch.zeros(6, dtype=torch.int32, device=dev)
+            ptr = lambda t: None if t is None else t.data_ptr()
+            _lib.check(fn_dev(self.h, C.byref(cfg), ptr(ct), ptr(sd), S, ptr(field), ptr(par), ptr(std), torch.cuda.current_stream(dev).cuda_stream))
+            sv = std.cpu().numpy()
+            st.converged, st.rounds, st.n_bad_seeds = int(sv[0]), int(sv[1]), int(sv[4])
+            st.tile_visits = int(sv[2:4].view(np.int64)[0])
+        else:
+            field = np.empty(shape, np.uint32)
+            par = np.empty(shape, np.uint8) if parent else None
+            _lib.check(fn_host(self.h, C.byref(cfg), _vp(cost), _vp(seeds) if S else None, S, _vp(field), _vp(par), C.byref(st)))
+        out = {"field": field, "converged": int(st.converged), "rounds": int(st.rounds), "tile_visits": int(st.tile_visits), "n_bad_seeds": int(st.n_bad_seeds),
+               "goals": seeds, "neutral": int(neutral), "lethal": int(lethal), "connectivity": int(connectivity)}
+        if par is not None:
+            out["parent"] = par
+        return out
+
+    def _nav_paths_call(self, who, field_who, shape_text, cfg_cls, fn_host, fn_dev, width, field_result, starts, max_len):
+        """who, field_who: the names of the method and of the one that makes its fields, in messages; shape_text: the refusal of a field that does not
+        have three axes, or None; width: the components of a path cell."""
+        if "parent" not in field_result:
+            raise ValueError(f"{who}: the field was computed without parents ({field_who}(parent=True))")
+        field, par = field_result["field"], field_result["parent"]
+        s = starts.cpu().numpy() if hasattr(starts, "is_cuda") else np.asarray(starts)
+        if s.size == 0:
+            s = np.zeros((0, 3), np.int32)
+        if s.ndim != 2 or s.shape[1] != 3:
+            raise ValueError(f"{who}: starts must be [P, 3]")
+        s = np.ascontiguousarray(np.clip(s.astype(np.int64), -(1 << 31), (1 << 31) - 1).astype(np.int32))
+        P, L = s.shape[0], int(max_len)
+        if shape_text is not None and len(field.shape) != 3:
+            raise ValueError(f"{who}: the field must be {shape_text}")
+        d0, d1, d2 = tuple(field.shape)
+        cfg = cfg_cls(d0, d1, d2)
+        Lc = max(L, 0)
+        if hasattr(field, "is_cuda"):
+            torch = _torch()
+            dev = field.device
+            cells = torch.empty((P, Lc, width), dtype=torch.int16, device=dev)
+            length = torch.empty(P, dtype=torch.int32, device=dev)
+            status = torch.empty(P, dtype=torch.uint8, device=dev)
+            cost = torch.empty(P, dtype=getattr(torch, "uint32", torch.int32), device=dev)
+            sd = torch.from_numpy(s).to(dev) if P else None
+            _lib.check(fn_dev(self.h, C.byref(cfg), field.data_ptr(), par.data_ptr(), sd.data_ptr() if P else None, P, L, cells.data_ptr(), length.data_ptr(),
+                              status.data_ptr(), cost.data_ptr(), torch.cuda.current_stream(dev).cuda_stream))
+        else:
+            field, par = np.ascontiguousarray(field, dtype=np.uint32), np.ascontiguousarray(par, dtype=np.uint8)
+            cells = np.empty((P, Lc, width), np.int16)
+            length, status, cost = np.empty(P, np.int32), np.empty(P, np.uint8), np.empty(P, np.uint32)
+            _lib.check(fn_host(self.h, C.byref(cfg), _vp(field), _vp(par), _vp(s) if P else None, P, L, _vp(cells), _vp(length), _vp(status), _vp(cost)))
+        return {"cells": cells, "length": length, "status": status, "cost": cost}
+
     # ---- cost-to-go fields and paths (tsl_nav_field.hip, DESIGN.md section 4.16) ------------------------------------------------
     def nav_field(self, cost, goals, neutral=50, lethal=253, connectivity=8, parent=True, max_rounds=None, rounds_fixed=0, check_every=None, device=False):
         """The cost-to-go field over 2-D cost planes: for every cell the least cost of getting to a goal, and which cells reach none.  cost: the `cost`
@@ -1104,65 +1202,9 @@ class DenseTSDF(BaseMap):
         bounds.  rounds_fixed > 0 runs exactly that many rounds and reads nothing in between.  numpy in gives numpy out; torch device tensors in (or
         device=True) give tensors out, ordered with torch.cuda.current_stream (tsl_tsdf_nav_field_dev: asynchronous with rounds_fixed > 0, and the
         statistics are then read, which waits)."""
-        if isinstance(cost, dict):
-            cost = cost["cost"]
-        on_dev = hasattr(cost, "is_cuda")
-        if on_dev or device:
-            torch = _torch()
-            dev = torch.device(f"cuda:{self.device}")
-            ct = cost if on_dev else torch.from_numpy(np.ascontiguousarray(np.asarray(cost, dtype=np.uint8)))
-            if ct.dtype != torch.uint8:
-                raise ValueError("nav_field: cost must be uint8")
-            ct = ct.to(dev).contiguous()
-            shape = tuple(ct.shape)
-        else:
-            cost = np.asarray(cost)
-            if cost.dtype != np.uint8:
-                raise ValueError("nav_field: cost must be uint8")
-            cost = np.ascontiguousarray(cost)
-            shape = cost.shape
-        if len(shape) == 2:
-            shape = (1,) + tuple(shape)
-        if len(shape) != 3:
-            raise ValueError("nav_field: cost must be [H, W] or [B, H, W]")
-        g = goals.cpu().numpy() if hasattr(goals, "is_cuda") else np.asarray(goals)
-        if g.size == 0:
-            g = np.zeros((0, 4), np.int32)
-        if g.ndim != 2 or g.shape[1] not in (3, 4):
-            raise ValueError("nav_field: goals must be [S, 3] or [S, 4]")
-        g4 = np.zeros((g.shape[0], 4), np.int64)
-        g4[:, :g.shape[1]] = g
-        seeds = np.ascontiguousarray((g4 & 0xffffffff).astype(np.uint32).view(np.int32))
-        seeds[:, :3] = np.clip(g4[:, :3], -(1 << 31), (1 << 31) - 1).astype(np.int32)
-        cfg = _lib.NavFieldCfg()
-        cfg.B, cfg.H, cfg.W = shape
-        cfg.neutral, cfg.lethal, cfg.connectivity = int(neutral), int(lethal), int(connectivity)
-        cfg.max_rounds = 0 if max_rounds is None else int(max_rounds)
-        if max_rounds is not None and int(max_rounds) == 0:
-            raise ValueError("nav_field: max_rounds must be at least 1")
-        cfg.rounds_fixed = int(rounds_fixed)
-        cfg.check_every = 0 if check_every is None else int(check_every)
-        S = seeds.shape[0]
-        st = _lib.NavFieldStats()
-        if on_dev or device:
-            field = torch.empty(shape, dtype=getattr(torch, "uint32", torch.int32), device=dev)
-            par = torch.empty(shape, dtype=torch.uint8, device=dev) if parent else None
-            sd = torch.from_numpy(seeds).to(dev) if S else None
-            std = torch.zeros(6, dtype=torch.int32, device=dev)
-            ptr = lambda t: None if t is None else t.data_ptr()
-            _lib.check(self.L.tsl_tsdf_nav_field_dev(self.h, C.byref(cfg), ptr(ct), ptr(sd), S, ptr(field), ptr(par), ptr(std), torch.cuda.current_stream(dev).cuda_stream))
-            sv = std.cpu().numpy()
-            st.converged, st.rounds, st.n_bad_seeds = int(sv[0]), int(sv[1]), int(sv[4])
-            st.tile_visits = int(sv[2:4].view(np.int64)[0])
-        else:
-            field = np.empty(shape, np.uint32)
-            par = np.empty(shape, np.uint8) if parent else None
-            _lib.check(self.L.tsl_tsdf_nav_field(self.h, C.byref(cfg), _vp(cost), _vp(seeds) if S else None, S, _vp(field), _vp(par), C.byref(st)))
-        out = {"field": field, "converged": int(st.converged), "rounds": int(st.rounds), "tile_visits": int(st.tile_visits), "n_bad_seeds": int(st.n_bad_seeds),
-               "goals": seeds, "neutral": int(neutral), "lethal": int(lethal), "connectivity": int(connectivity)}
-        if par is not None:
-            out["parent"] = par
-        return out
+        return self._nav_field_call("nav_field", lambda s: (1,) + s if len(s) == 2 else (s if len(s) == 3 else None), "[H, W] or [B, H, W]", _lib.NavFieldCfg,
+                                    _lib.NavFieldStats, self.L.tsl_tsdf_nav_field, self.L.tsl_tsdf_nav_field_dev, cost, goals, neutral, lethal, connectivity, parent,
+                                    max_rounds, rounds_fixed, check_every, device)
 
     def nav_paths(self, field_result, starts, max_len):
         """The cheapest way to a goal from every start, along the parents of a nav_field result (computed with parent=True).  starts: [P, 3] = plane, row,
@@ -1170,36 +1212,8 @@ class DenseTSDF(BaseMap):
         start on, -1 past the end; `length` int32 [P]; `status` u8 [P] (0 = ended on a goal, 1 = truncated at max_len, 2 = the start is unreached or a
         wall, 3 = the start is outside); `cost` uint32 [P] = the field at the start.  A result of torch tensors gives tensors, asynchronously on
         torch.cuda.current_stream (tsl_tsdf_nav_field_paths_dev); otherwise numpy arrays."""
-        if "parent" not in field_result:
-            raise ValueError("nav_paths: the field was computed without parents (nav_field(parent=True))")
-        field, par = field_result["field"], field_result["parent"]
-        s = starts.cpu().numpy() if hasattr(starts, "is_cuda") else np.asarray(starts)
-        if s.size == 0:
-            s = np.zeros((0, 3), np.int32)
-        if s.ndim != 2 or s.shape[1] != 3:
-            raise ValueError("nav_paths: starts must be [P, 3]")
-        s = np.ascontiguousarray(np.clip(s.astype(np.int64), -(1 << 31), (1 << 31) - 1).astype(np.int32))
-        P, L = s.shape[0], int(max_len)
-        cfg = _lib.NavFieldCfg()
-        cfg.B, cfg.H, cfg.W = tuple(field.shape)
-        Lc = max(L, 0)
-        if hasattr(field, "is_cuda"):
-            torch = _torch()
-            dev = field.device
-            cells = torch.empty((P, Lc, 2), dtype=torch.int16, device=dev)
-            length = torch.empty(P, dtype=torch.int32, device=dev)
-            status = torch.empty(P, dtype=torch.uint8, device=dev)
-            cost = torch.empty(P, dtype=getattr(torch, "uint32", torch.int32), device=dev)
-            sd = torch.from_numpy(s).to(dev) if P else None
-            _lib.check(self.L.tsl_tsdf_nav_field_paths_dev(self.h, C.byref(cfg), field.data_ptr(), par.data_ptr(), sd.data_ptr() if P else None, P, L, cells.data_ptr(),
-                                                           length.data_ptr(), status.data_ptr(), cost.data_ptr(), torch.cuda.current_stream(dev).cuda_stream))
-        else:
-            field, par = np.ascontiguousarray(field, dtype=np.uint32), np.ascontiguousarray(par, dtype=np.uint8)
-            cells = np.empty((P, Lc, 2), np.int16)
-            length, status, cost = np.empty(P, np.int32), np.empty(P, np.uint8), np.empty(P, np.uint32)
-            _lib.check(self.L.tsl_tsdf_nav_field_paths(self.h, C.byref(cfg), _vp(field), _vp(par), _vp(s) if P else None, P, L, _vp(cells), _vp(length), _vp(status),
-                                                       _vp(cost)))
-        return {"cells": cells, "length": length, "status": status, "cost": cost}
+        return self._nav_paths_call("nav_paths", "nav_field", None, _lib.NavFieldCfg, self.L.tsl_tsdf_nav_field_paths, self.L.tsl_tsdf_nav_field_paths_dev, 2,
+                                    field_result, starts, max_len)
 
     # ---- 3-D cost-to-go fields and paths over flight volumes (tsl_nav_field3.hip, DESIGN.md section 4.18) -----------------------
     def nav_field3d(self, cost, goals, neutral=50, lethal=253, connectivity=26, parent=True, max_rounds=None, rounds_fixed=0, check_every=None, device=False):
@@ -1213,63 +1227,9 @@ class DenseTSDF(BaseMap):
         dk = 0, 8 = up, 9 .. 16 the same eight with dk = 1, 17 = down, 18 .. 25 with dk = -1), `converged`, `rounds`, `tile_visits`, `n_bad_seeds`, and
         `goals` (int32 [S, 4]) and the parameters, for nav_paths3d.  Rounds, max_rounds (None = min(4 * tiles + 64, 65536)), rounds_fixed, check_every
         and the numpy / torch forms are nav_field's."""
-        if isinstance(cost, dict):
-            cost = cost["cost"]
-        on_dev = hasattr(cost, "is_cuda")
-        if on_dev or device:
-            torch = _torch()
-            dev = torch.device(f"cuda:{self.device}")
-            ct = cost if on_dev else torch.from_numpy(np.ascontiguousarray(np.asarray(cost, dtype=np.uint8)))
-            if ct.dtype != torch.uint8:
-                raise ValueError("nav_field3d: cost must be uint8")
-            ct = ct.to(dev).contiguous()
-            shape = tuple(ct.shape)
-        else:
-            cost = np.asarray(cost)
-            if cost.dtype != np.uint8:
-                raise ValueError("nav_field3d: cost must be uint8")
-            cost = np.ascontiguousarray(cost)
-            shape = cost.shape
-        if len(shape) != 3:
-            raise ValueError("nav_field3d: cost must be [D, H, W]")
-        g = goals.cpu().numpy() if hasattr(goals, "is_cuda") else np.asarray(goals)
-        if g.size == 0:
-            g = np.zeros((0, 4), np.int32)
-        if g.ndim != 2 or g.shape[1] not in (3, 4):
-            raise ValueError("nav_field3d: goals must be [S, 3] or [S, 4]")
-        g4 = np.zeros((g.shape[0], 4), np.int64)
-        g4[:, :g.shape[1]] = g
-        seeds = np.ascontiguousarray((g4 & 0xffffffff).astype(np.uint32).view(np.int32))
-        seeds[:, :3] = np.clip(g4[:, :3], -(1 << 31), (1 << 31) - 1).astype(np.int32)
-        cfg = _lib.NavField3Cfg()
-        cfg.D, cfg.H, cfg.W = shape
-        cfg.neutral, cfg.lethal, cfg.connectivity = int(neutral), int(lethal), int(connectivity)
-        cfg.max_rounds = 0 if max_rounds is None else int(max_rounds)
-        if max_rounds is not None and int(max_rounds) == 0:
-            raise ValueError("nav_field3d: max_rounds must be at least 1")
-        cfg.rounds_fixed = int(rounds_fixed)
-        cfg.check_every = 0 if check_every is None else int(check_every)
-        S = seeds.shape[0]
-        st = _lib.NavField3Stats()
-        if on_dev or device:
-            field = torch.empty(shape, dtype=getattr(torch, "uint32", torch.int32), device=dev)
-            par = torch.empty(shape, dtype=torch.uint8, device=dev) if parent else None
-            sd = torch.from_numpy(seeds).to(dev) if S else None
-            std = torch.zeros(6, dtype=torch.int32, device=dev)
-            ptr = lambda t: None if t is None else t.data_ptr()
-            _lib.check(self.L.tsl_tsdf_nav_field3_dev(self.h, C.byref(cfg), ptr(ct), ptr(sd), S, ptr(field), ptr(par), ptr(std), torch.cuda.current_stream(dev).cuda_stream))
-            sv = std.cpu().numpy()
-            st.converged, st.rounds, st.n_bad_seeds = int(sv[0]), int(sv[1]), int(sv[4])
-            st.tile_visits = int(sv[2:4].view(np.int64)[0])
-        else:
-            field = np.empty(shape, np.uint32)
-            par = np.empty(shape, np.uint8) if parent else None
-            _lib.check(self.L.tsl_tsdf_nav_field3(self.h, C.byref(cfg), _vp(cost), _vp(seeds) if S else None, S, _vp(field), _vp(par), C.byref(st)))
-        out = {"field": field, "converged": int(st.converged), "rounds": int(st.rounds), "tile_visits": int(st.tile_visits), "n_bad_seeds": int(st.n_bad_seeds),
-               "goals": seeds, "neutral": int(neutral), "lethal": int(lethal), "connectivity": int(connectivity)}
-        if par is not None:
-            out["parent"] = par
-        return out
+        return self._nav_field_call("nav_field3d", lambda s: s if len(s) == 3 else None, "[D, H, W]", _lib.NavField3Cfg, _lib.NavField3Stats,
+                                    self.L.tsl_tsdf_nav_field3, self.L.tsl_tsdf_nav_field3_dev, cost, goals, neutral, lethal, connectivity, parent, max_rounds,
+                                    rounds_fixed, check_every, device)
 
     def nav_paths3d(self, field_result, starts, max_len):
         """nav_paths in 3-D: the cheapest way to a goal from every start, along the parents of a nav_field3d result (computed with parent=True).
@@ -1277,38 +1237,8 @@ class DenseTSDF(BaseMap):
         `length` int32 [P]; `status` u8 [P] (0 = ended on a goal, 1 = truncated at max_len, 2 = the start is unreached or a wall, 3 = the start is
         outside); `cost` uint32 [P] = the field at the start.  A result of torch tensors gives tensors, asynchronously on torch.cuda.current_stream
         (tsl_tsdf_nav_field3_paths_dev); otherwise numpy arrays."""
-        if "parent" not in field_result:
-            raise ValueError("nav_paths3d: the field was computed without parents (nav_field3d(parent=True))")
-        field, par = field_result["field"], field_result["parent"]
-        s = starts.cpu().numpy() if hasattr(starts, "is_cuda") else np.asarray(starts)
-        if s.size == 0:
-            s = np.zeros((0, 3), np.int32)
-        if s.ndim != 2 or s.shape[1] != 3:
-            raise ValueError("nav_paths3d: starts must be [P, 3]")
-        s = np.ascontiguousarray(np.clip(s.astype(np.int64), -(1 << 31), (1 << 31) - 1).astype(np.int32))
-        P, L = s.shape[0], int(max_len)
-        if len(field.shape) != 3:
-            raise ValueError("nav_paths3d: the field must be [D, H, W]")
-        cfg = _lib.NavField3Cfg()
-        cfg.D, cfg.H, cfg.W = tuple(field.shape)
-        Lc = max(L, 0)
-        if hasattr(field, "is_cuda"):
-            torch = _torch()
-            dev = field.device
-            cells = torch.empty((P, Lc, 3), dtype=torch.int16, device=dev)
-            length = torch.empty(P, dtype=torch.int32, device=dev)
-            status = torch.empty(P, dtype=torch.uint8, device=dev)
-            cost = torch.empty(P, dtype=getattr(torch, "uint32", torch.int32), device=dev)
-            sd = torch.from_numpy(s).to(dev) if P else None
-            _lib.check(self.L.tsl_tsdf_nav_field3_paths_dev(self.h, C.byref(cfg), field.data_ptr(), par.data_ptr(), sd.data_ptr() if P else None, P, L, cells.data_ptr(),
-                                                            length.data_ptr(), status.data_ptr(), cost.data_ptr(), torch.cuda.current_stream(dev).cuda_stream))
-        else:
-            field, par = np.ascontiguousarray(field, dtype=np.uint32), np.ascontiguousarray(par, dtype=np.uint8)
-            cells = np.empty((P, Lc, 3), np.int16)
-            length, status, cost = np.empty(P, np.int32), np.empty(P, np.uint8), np.empty(P, np.uint32)
-            _lib.check(self.L.tsl_tsdf_nav_field3_paths(self.h, C.byref(cfg), _vp(field), _vp(par), _vp(s) if P else None, P, L, _vp(cells), _vp(length), _vp(status),
-                                                        _vp(cost)))
-        return {"cells": cells, "length": length, "status": status, "cost": cost}
+        return self._nav_paths_call("nav_paths3d", "nav_field3d", "[D, H, W]", _lib.NavField3Cfg, self.L.tsl_tsdf_nav_field3_paths,
+                                    self.L.tsl_tsdf_nav_field3_paths_dev, 3, field_result, starts, max_len)
 
     def flight_volume(self, stride=4, z_range=None, lut=None, cost_unknown=255, cost_outside=255, refresh=True, device=False):
         """The cost volume of nav_field3d from the ESDF: a lattice of one sample per cell of `stride`^3 voxels, through query_esdf(interpolate=False)

@@ -48,6 +48,30 @@ def terrain_slope_deg(slope2, slope_base_vox):
 NAV_UNREACHED = 0xffffffff
 
 
+def _host(a):
+    return np.asarray(a.cpu().numpy() if hasattr(a, "cpu") else a)
+
+
+def _cluster_least(frontiers, f, ok, cell):
+    """The shared tail of frontier_reach and frontier_reach3d: per cluster the least f[cell] over the frontier rows with ok, the first row on a tie.
+    cell: one index array per axis of f, a row of frontiers["indices"] each."""
+    if f.dtype == np.int32:                                      # a torch build without uint32 hands the bits over as int32
+        f = f.view(np.uint32)
+    cl = _host(frontiers["cluster"]).astype(np.int64).reshape(-1)
+    m = len(frontiers["clusters"])
+    value = np.full(m, NAV_UNREACHED, np.uint32)
+    voxel = np.full(m, -1, np.int64)
+    rows = np.nonzero(ok)[0]
+    if rows.size:
+        v = f[tuple(c[rows] for c in cell)].astype(np.int64)
+        order = np.lexsort((rows, v, cl[rows]))                  # by cluster, then value, then row
+        first = order[np.concatenate([[True], np.diff(cl[rows][order]) != 0])]
+        hit = v[first] != NAV_UNREACHED
+        value[cl[rows][first][hit]] = v[first][hit].astype(np.uint32)
+        voxel[cl[rows][first][hit]] = rows[first][hit]
+    return {"value": value, "voxel": voxel, "reached": value != NAV_UNREACHED}
+
+
 def frontier_reach(frontiers, field_result, band, N=None, plane=0):
     """Which frontier clusters can be reached, and how cheaply: per cluster of a DenseTSDF.extract_frontiers result the least value of a DenseTSDF.nav_field
     result over the columns (i + N / 2, j + N / 2) of the cluster's voxels whose layer k lies in band = (k_min, k_max), both ends inclusive -- the band
@@ -55,29 +79,15 @@ def frontier_reach(frontiers, field_result, band, N=None, plane=0):
     plane: the plane of the field to read.  Host numpy; tensors are copied.  Returns a dict: `value` uint32 [m] (NAV_UNREACHED for a cluster that has
     no voxel in the band or reaches nothing), `voxel` int64 [m] (the row of frontiers["indices"] that attains it, the first in the frontiers' order
     on a tie; -1 with NAV_UNREACHED), `reached` bool [m]."""
-    def host(a):
-        return np.asarray(a.cpu().numpy() if hasattr(a, "cpu") else a)
-    field = host(field_result["field"] if isinstance(field_result, dict) else field_result)
+    field = _host(field_result["field"] if isinstance(field_result, dict) else field_result)
     if field.ndim == 2:
         field = field[None]
     f = field[int(plane)]
     N = int(f.shape[0] if N is None else N)
-    idx = host(frontiers["indices"]).astype(np.int64).reshape(-1, 3)
-    cl = host(frontiers["cluster"]).astype(np.int64).reshape(-1)
-    m = len(frontiers["clusters"])
-    value = np.full(m, NAV_UNREACHED, np.uint32)
-    voxel = np.full(m, -1, np.int64)
+    idx = _host(frontiers["indices"]).astype(np.int64).reshape(-1, 3)
     ui, uj = idx[:, 0] + N // 2, idx[:, 1] + N // 2
     ok = (idx[:, 2] >= int(band[0])) & (idx[:, 2] <= int(band[1])) & (ui >= 0) & (ui < f.shape[0]) & (uj >= 0) & (uj < f.shape[1])
-    rows = np.nonzero(ok)[0]
-    if rows.size:
-        v = f[ui[rows], uj[rows]].astype(np.int64)
-        order = np.lexsort((rows, v, cl[rows]))                  # by cluster, then value, then row
-        first = order[np.concatenate([[True], np.diff(cl[rows][order]) != 0])]
-        hit = v[first] != NAV_UNREACHED
-        value[cl[rows][first][hit]] = v[first][hit].astype(np.uint32)
-        voxel[cl[rows][first][hit]] = rows[first][hit]
-    return {"value": value, "voxel": voxel, "reached": value != NAV_UNREACHED}
+    return _cluster_least(frontiers, f, ok, (ui, uj))
 
 
 # ---- 3-D: flight volumes for DenseTSDF.nav_field3d (DESIGN.md section 4.18) ----------------------------------------------------------------------
@@ -128,30 +138,14 @@ def frontier_reach3d(frontiers, field_result, volume):
     do not count.  Host numpy; tensors are copied.  Returns the dict of frontier_reach: `value` uint32 [m] (NAV_UNREACHED for a cluster that has no voxel
     in the volume or reaches nothing), `voxel` int64 [m] (the row of frontiers["indices"] that attains it, the first in the frontiers' order on a tie;
     -1 with NAV_UNREACHED), `reached` bool [m]."""
-    def host(a):
-        return np.asarray(a.cpu().numpy() if hasattr(a, "cpu") else a)
-    f = host(field_result["field"] if isinstance(field_result, dict) else field_result)
-    if f.dtype == np.int32:                                      # a torch build without uint32 hands the bits over as int32
-        f = f.view(np.uint32)
+    f = _host(field_result["field"] if isinstance(field_result, dict) else field_result)
     if f.ndim != 3:
         raise ValueError("frontier_reach3d: the field must be [D, H, W]")
     s = int(volume["stride"])
     org, half = [int(v) for v in volume["origin"]], [int(v) for v in volume["half"]]
-    idx = host(frontiers["indices"]).astype(np.int64).reshape(-1, 3)
-    cl = host(frontiers["cluster"]).astype(np.int64).reshape(-1)
-    m = len(frontiers["clusters"])
-    value = np.full(m, NAV_UNREACHED, np.uint32)
-    voxel = np.full(m, -1, np.int64)
+    idx = _host(frontiers["indices"]).astype(np.int64).reshape(-1, 3)
     ck = (idx[:, 2] + half[0] - org[0]) // s
     ci = (idx[:, 0] + half[1] - org[1]) // s
     cj = (idx[:, 1] + half[2] - org[2]) // s
     ok = (ck >= 0) & (ck < f.shape[0]) & (ci >= 0) & (ci < f.shape[1]) & (cj >= 0) & (cj < f.shape[2])
-    rows = np.nonzero(ok)[0]
-    if rows.size:
-        v = f[ck[rows], ci[rows], cj[rows]].astype(np.int64)
-        order = np.lexsort((rows, v, cl[rows]))                  # by cluster, then value, then row
-        first = order[np.concatenate([[True], np.diff(cl[rows][order]) != 0])]
-        hit = v[first] != NAV_UNREACHED
-        value[cl[rows][first][hit]] = v[first][hit].astype(np.uint32)
-        voxel[cl[rows][first][hit]] = rows[first][hit]
-    return {"value": value, "voxel": voxel, "reached": value != NAV_UNREACHED}
+    return _cluster_least(frontiers, f, ok, (ck, ci, cj))

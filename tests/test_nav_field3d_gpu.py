@@ -151,6 +151,72 @@ def test_one_layer_equals_nav_field(hip_lib):
         assert np.array_equal(three["parent"], np.where(two["parent"] == 8, 26, two["parent"])), c3
 
 
+def _interleaved_calls():
+    """the calls of the two tests below with their restatements, computed once: a 2-D field over [2, 33, 40], a 3-D field over [9, 17, 33], a larger 2-D
+    field over [1, 70, 65] and the 3-D call again.  Every shape is one partial tile beyond a tile edge on each axis: the smallest at which both round
+    kernels use halo tiles and the activity map has more than one word per axis."""
+    import nav_field_ref as ref2
+    import nav_field_scenes as sc2
+    if "interleaved" not in _REF:
+        p0, p1 = sc2.random_plane(33, 40), sc2.random_plane(33, 40, seed=8)
+        two = np.stack([p0[0], p1[0]])
+        g2 = np.array([[0, p0[1][0, 1], p0[1][0, 2], 0], [1, p1[1][0, 1], p1[1][0, 2], 40], [2, 0, 0, 0]], np.int32)      # a goal per plane, one in a plane that is not there
+        c3, g3, _ = sc.random_volume(9, 17, 33)
+        big, gb, _ = sc2.random_plane(70, 65)
+        calls = [("nav_field", two, g2, ref2.field_and_parent(two, g2)), ("nav_field3d", c3, g3, ref.field_and_parent(c3, g3)),
+                 ("nav_field", big[None], gb, ref2.field_and_parent(big, gb))]
+        for c in calls:
+            for a in ("field", "parent"):
+                c[3][a].setflags(write=False)
+        _REF["interleaved"] = calls + [calls[1]]
+    return _REF["interleaved"]
+
+
+def test_interleaved_2d_and_3d_calls_on_one_handle_keep_their_scratch_apart(hip_lib):
+    """the two solvers are two instances of one state type behind one grow helper: calls that alternate between them, and a 2-D call that outgrows the
+    scratch of the one before, must each see their own buffers -- in the numpy form and in the device form"""
+    import torch
+    g = _map()
+    host = []
+    for how, cost, goals, want in _interleaved_calls():
+        got = getattr(g, how)(cost, goals)
+        _equal(got, want, f"{how} {cost.shape}")
+        assert got["n_bad_seeds"] == (1 if cost.shape[0] == 2 else 0) and 1 <= got["rounds"] and got["tile_visits"] >= got["rounds"]
+        host.append(got)
+    assert host[3]["field"].tobytes() == host[1]["field"].tobytes() and host[3]["parent"].tobytes() == host[1]["parent"].tobytes()
+    dev = []
+    for (how, cost, goals, want), h in zip(_interleaved_calls(), host):
+        fixed = h["rounds"] + 4                                                           # (a halo read that races a write-back may move the last change by a round)
+        got = getattr(g, how)(torch.from_numpy(cost).cuda(), goals, rounds_fixed=fixed)
+        assert got["field"].is_cuda and got["parent"].is_cuda and 1 <= got["rounds"] <= fixed and got["tile_visits"] >= got["rounds"]
+        dev.append({**got, "field": got["field"].cpu().numpy().view(np.uint32), "parent": got["parent"].cpu().numpy()})
+        _equal(dev[-1], want, f"{how} {cost.shape}, device form")
+    assert dev[3]["field"].tobytes() == dev[1]["field"].tobytes() and dev[3]["parent"].tobytes() == dev[1]["parent"].tobytes()
+
+
+def test_profiling_ids_count_the_2d_launches_and_none_of_the_3d(hip_lib):
+    """one bracket per seed pass, per round, per parent pass (the seed-parent pass inside it) and per paths launch of the 2-D solver; the 3-D solver has
+    no id and adds nothing to them"""
+    import torch
+    g = _map()
+    ids = [_lib.K_NAV_FIELD_SEED, _lib.K_NAV_FIELD_ROUND, _lib.K_NAV_FIELD_PARENT, _lib.K_NAV_FIELD_PATHS]
+    (_, cost2, goals2, _), (_, cost3, goals3, _) = _interleaved_calls()[:2]
+    g.enable_profiling(True, only=ids)
+    try:
+        for k in ids:
+            g.kernel_time(k)                                                              # (a query returns what was recorded since the one before)
+        res = g.nav_field(torch.from_numpy(cost2).cuda(), goals2, rounds_fixed=3)
+        g.nav_paths(res, goals2[:1, :3], 16)
+        got = [g.kernel_time(k) for k in ids]
+        print("nav_field profiling (ms, launches) of seed, round, parent, paths:", got)
+        assert [n for _, n in got] == [1, 3, 1, 1] and all(ms > 0.0 for ms, _ in got)
+        res3 = g.nav_field3d(torch.from_numpy(cost3).cuda(), goals3, rounds_fixed=3)
+        g.nav_paths3d(res3, goals3[:1, :3], 16)
+        assert [g.kernel_time(k)[1] for k in ids] == [0, 0, 0, 0]
+    finally:
+        g.enable_profiling(False)
+
+
 def test_two_calls_give_identical_bytes(hip_lib):
     cost, goals, _ = sc.random_volume(*sc.SHAPES[4])
     a, b = _map().nav_field3d(cost, goals), _map().nav_field3d(cost, goals)

@@ -119,6 +119,13 @@ def test_frontier_reach_on_a_hand_made_cluster_list():
     assert got["voxel"].tolist() == [1, 3, -1, -1, -1] and got["reached"].tolist() == [True, True, False, False, False]
     wide = frontier_reach(fr, field[1], (0, 9))                 # a bare plane, N from its shape
     assert wide["value"].tolist() == [300, 40, ref.UNREACHED, 7, ref.UNREACHED] and wide["voxel"].tolist() == [1, 3, -1, 6, -1]
+    # a torch build without uint32 hands the field's bits over as int32, -1 in an unreached cell: the same answer
+    signed = field.view(np.int32)
+    assert signed.dtype == np.int32 and signed[1, 5, 5] == -1
+    for args, kw, want in (((fr, {"field": signed}, (0, 2), N), dict(plane=1), got), ((fr, signed[1], (0, 9)), {}, wide)):
+        again = frontier_reach(*args, **kw)
+        for k in ("value", "voxel", "reached"):
+            assert again[k].dtype == want[k].dtype and np.array_equal(again[k], want[k]), k
 
 
 def test_bindings_header_and_refusals_that_need_no_device():
