@@ -1222,6 +1222,7 @@ int64_t ora_esdf_compute(const ora_tsdf* m, float gamma, float max_dist, int16_t
             if (nid < 0) continue;
             int nsg = sgn_f(tbuf[nid]); if (nsg == 0) nsg = 1;
             if (nsg != sg) continue;             /* distances only propagate within one side of the surface (:289,:295) */
+            if (fabsf(tbuf[nid]) < gamma) continue;      /* a band voxel is fixed: never a target, and it feeds its neighbours with |TSDF| (matters for gamma > voxel: step >= voxel > |TSDF| otherwise) */
             float step = sqrtf((float)(di * di + dj * dj + dk * dk)) * vs;               /* :286 */
             float nd = it.d + step;
             if (nd < mag[nid]) { mag[nid] = nd; heap_push(&hp, nd, nid); }

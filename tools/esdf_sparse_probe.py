@@ -9,18 +9,7 @@ from taichislam_amd import _lib
 from taichislam_amd.mapping import DenseTSDF
 from taichislam_amd.utils import synthetic as syn
 from util import C2, lin
-
-def ball_depth(R, T, base, centre, rad):
-    fx, fy, cx, cy = syn.K_DEPTH[0], syn.K_DEPTH[4], syn.K_DEPTH[2], syn.K_DEPTH[5]
-    h, w = base.shape
-    ii, jj = np.meshgrid(np.arange(w, dtype=np.float64), np.arange(h, dtype=np.float64))
-    d = np.stack([(ii - cx) / fx, (jj - cy) / fy, np.ones_like(ii)], axis=-1) @ R.T
-    oc = T - centre
-    a = (d * d).sum(-1); b = 2.0 * (d @ oc); c = float(oc @ oc) - rad * rad
-    disc = b * b - 4 * a * c
-    t = np.where(disc > 0, (-b - np.sqrt(np.maximum(disc, 0))) / (2 * a), np.inf)
-    mm = np.where((t > 0) & np.isfinite(t), np.rint(1000.0 * t), 65535.0)
-    return np.minimum(base.astype(np.float64), mm).astype(np.uint16)
+from esdf_scenes import ball_depth          # (tests/esdf_scenes.py: the suite runs the same scene at small size)
 
 N, WARM = 60, 20
 R, T = syn.camera_pose(0)
