@@ -789,6 +789,58 @@ int  tsl_tsdf_nav_field3_paths(tsl_tsdf* m, const tsl_nav_field3_cfg* cfg, const
 int  tsl_tsdf_nav_field3_paths_dev(tsl_tsdf* m, const tsl_nav_field3_cfg* cfg, const void* field_dev, const void* parent_dev, const void* starts_dev,
                                    int32_t n_starts, int32_t max_len, void* cells_dev, void* length_dev, void* status_dev, void* cost_dev, void* user_stream);
 
+/* ---- safe corridors: free boxes around cells and along paths (tsl_nav_corridor.hip): the step between a path of
+ * tsl_tsdf_nav_field_paths / tsl_tsdf_nav_field3_paths -- a staircase of cells that hugs obstacles -- and a corridor-based trajectory optimiser, which asks
+ * for a short sequence of overlapping convex free regions that contains the path.  The region is the axis-aligned box inflated around a cell until a face
+ * meets an obstacle.  The volume is the CALLER'S; the handle supplies only the device, the stream and scratch (allocated by the first call, released with
+ * the handle); no map is read.  Everything is integer and the face order makes the answer unique: tests/nav_corridor_ref.py restates it byte for byte.
+ *   Volume: cost u8 [D][H][W]: layer k, row i, column j, the axes of tsl_tsdf_nav_field3; 1 <= D, H, W <= 4096 and D * H * W <= 2^28 (the 16 planes of 4096 x
+ *     4096 of tsl_tsdf_nav_field: D is then the number of planes).  A cell is free when it is inside and cost < free_below, free_below in 1 .. 255: the
+ *     `lethal` of the field, or less, to keep a margin.
+ *   Extents: ext_k, ext_i, ext_j, each in 0 .. 127: the most a box may reach from its seed along that axis, in cells.  ext_k = 0 makes the layers
+ *     independent planes: the 2-D case.
+ *   Box of a seed cell c: c outside the volume: six times -1 and the flag TSL_BOX_OUTSIDE.  c not free: lo = hi = c and TSL_BOX_BLOCKED.  Otherwise the
+ *     box starts as lo = hi = c with all six faces open and grows in rounds.  In a round the open faces are tried in the fixed order -j, +j, -i, +i, -k, +k.
+ *     A try moves that face out by one cell; it succeeds when the new coordinate is within ext of c on that axis, it is inside the volume, and every cell
+ *     of the new slab is free -- the slab is one cell thick and spans the box as it stands at that moment on the other two axes, including what earlier
+ *     tries of the same round added.  A try that fails closes the face for good (the slab only ever gets wider).  Rounds repeat until no face is open: at
+ *     most 6 * (max ext + 1) tries.  The result is a free box that contains c and that no single face move can enlarge within ext; flag 0.
+ *   boxes int16 [S][6] = (k0, i0, j0, k1, i1, j1), both ends inclusive; flags u8 [S].  cells int32 [S][3] = (layer, row, col), 0 <= S <= 2^20; max_boxes is
+ *     not read by tsl_tsdf_nav_boxes / _dev.
+ *   Corridor of a path (tsl_tsdf_nav_corridor / _dev): cells int16 [P][L][3] = (layer, row, col), the `cells` of tsl_tsdf_nav_field3_paths (those of
+ *     tsl_tsdf_nav_field_paths with the plane in front); a path is the cells 0 .. len - 1 of its row, len = min(length[p], L).  0 <= P <= 2^16, 1 <= L <=
+ *     4096, P * L <= 2^22, max_boxes = Q in 1 .. L.  With B(s) the box of cell s: s_0 = 0; given s_q, B(s_q) is emitted with its seed index s_q; t_q is the
+ *     largest t >= s_q such that the cells s_q .. t all lie in B(s_q), and t_q = s_q when the seed is blocked or outside; t_q = len - 1 completes the
+ *     corridor: status 0; otherwise s_q+1 = t_q if t_q > s_q, else s_q + 1 (the seed index strictly increases); Q boxes without completing: status 1; len
+ *     <= 0: status 2 and no box.
+ *   boxes int16 [P][Q][6]; seed int32 [P][Q]; count int32 [P]; status u8 [P]; link u8 [P][Q]: 0 for a path's first box, 1 when the box shares at least one
+ *     cell with the box before it, 2 when it shares none (the box of a seed outside the volume has no cells), plus 4 when its seed is blocked or outside.
+ *     Rows past count: boxes and seed -1, link 255.  Link 2 happens -- t_q = s_q and the boxes of two adjacent path cells only touch: a diagonal move
+ *     between two cells whose boxes each stop at the other's row, or an axis move whose first slab had already been widened by an earlier face and so held
+ *     an obstacle.  The flag is the honest answer; a consumer that needs overlap splits there.
+ *   Kernels: the volume is packed into one free bit per cell (row pitch ceil(W / 64) words, 64-bit ballots: D * H * ceil(W / 64) * 8 bytes of scratch, an
+ *     eighth of the volume where W is a multiple of 64 and at worst, for W = 1, 8 bytes per cell -- 128 MB); one wave per seed inflates on bits -- the
+ *     corridor forms inflate EVERY cell of every path, P * L independent waves -- and one wave per path chains.  No atomics, no workgroup waits for
+ *     another, every loop has a bound known at launch.
+ * The host forms take host pointers, run on the handle's stream, wait and copy back.  The _dev forms take device pointers, are ordered with `user_stream`
+ * like tsl_tsdf_nav_field3_paths_dev and are ASYNCHRONOUS -- except that a call which has to allocate or grow the handle's scratch (the first call, and any
+ * call with a larger volume or more path cells than those before it) frees and allocates device memory and so waits for the device.  Every output is nullable.  S = 0 and P = 0 are no error.  These kernels have no
+ * tsl_tsdf_prof_query id; time them with events around the _dev calls (tools/bench_nav_corridor.py).
+ * TSL_ERR_ARG, before anything is launched or written (the text names the entry point): a null handle, cfg or cost; D, H or W outside 1 .. 4096 or more than
+ * 2^28 cells; free_below outside 1 .. 255; an ext outside 0 .. 127; S outside 0 .. 2^20; P outside 0 .. 2^16, L outside 1 .. 4096, P * L above 2^22; max_boxes
+ * outside 1 .. L (corridor forms); cells null while S or P > 0; length null while P > 0.  A refused call leaves the handle usable. */
+#define TSL_BOX_BLOCKED 1
+#define TSL_BOX_OUTSIDE 2
+typedef struct { int32_t D, H, W, free_below, ext_k, ext_i, ext_j, max_boxes; } tsl_nav_corridor_cfg;
+int  tsl_tsdf_nav_boxes(tsl_tsdf* m, const tsl_nav_corridor_cfg* cfg, const uint8_t* cost, const int32_t* cells /* [S][3] */, int32_t n, int16_t* boxes /* [S][6] */,
+                        uint8_t* flags);
+int  tsl_tsdf_nav_boxes_dev(tsl_tsdf* m, const tsl_nav_corridor_cfg* cfg, const void* cost_dev, const void* cells_dev, int32_t n, void* boxes_dev, void* flags_dev,
+                            void* user_stream);
+int  tsl_tsdf_nav_corridor(tsl_tsdf* m, const tsl_nav_corridor_cfg* cfg, const uint8_t* cost, const int16_t* cells /* [P][L][3] */, const int32_t* length, int32_t P,
+                           int32_t L, int16_t* boxes, int32_t* seed, uint8_t* link, int32_t* count, uint8_t* status);
+int  tsl_tsdf_nav_corridor_dev(tsl_tsdf* m, const tsl_nav_corridor_cfg* cfg, const void* cost_dev, const void* cells_dev, const void* length_dev, int32_t P, int32_t L,
+                               void* boxes_dev, void* seed_dev, void* link_dev, void* count_dev, void* status_dev, void* user_stream);
+
 /* ---- terrain layers for ground robots (tsl_nav_terrain.hip): per height band and (x, y) column the height of the surface a robot
  * can stand on, over the robot's footprint the step and the slope of that surface, and a class, a distance and a cost in the vocabulary of
  * tsl_tsdf_nav_grid, so that tsl_tsdf_nav_field and the OccupancyGrid adapters take them unchanged.  Where nav_grid calls a column an obstacle as soon as

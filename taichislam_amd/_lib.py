@@ -198,6 +198,16 @@ class NavField3Stats(C.Structure):
 NAV3_SEED = 26                  # TSL_NAV3_SEED: the parent code of a goal cell of DenseTSDF.nav_field3d
 
 
+class NavCorridorCfg(C.Structure):
+    """tsl_nav_corridor_cfg (tsl_tsdf_nav_boxes, tsl_tsdf_nav_corridor): a volume of D layers of H x W cells; a cell is free when cost < free_below (1 ..
+    255); ext_k, ext_i, ext_j in 0 .. 127: the reach of a box from its seed; max_boxes in 1 .. L (the corridor forms only)"""
+    _fields_ = [("D", C.c_int32), ("H", C.c_int32), ("W", C.c_int32), ("free_below", C.c_int32), ("ext_k", C.c_int32), ("ext_i", C.c_int32),
+                ("ext_j", C.c_int32), ("max_boxes", C.c_int32)]
+
+
+BOX_BLOCKED, BOX_OUTSIDE = 1, 2     # TSL_BOX_*: the flags of DenseTSDF.nav_boxes
+
+
 class NavTerrainCfg(C.Structure):
     """tsl_nav_terrain_cfg (tsl_tsdf_nav_terrain): the bands and free_thres of tsl_nav_cfg; clearance and free_run in layers above the support, pick 0 = the
     lowest / 1 = the highest standable layer, window and slope_base in cells, max_step in sixteenths of a voxel, max_slope2 = (tan * 128 * slope_base)^2
@@ -330,6 +340,10 @@ SIGNATURES = {
     "tsl_tsdf_nav_field3_dev": (C.c_int, [vp, C.POINTER(NavField3Cfg), vp, vp, i32, vp, vp, vp, vp]),
     "tsl_tsdf_nav_field3_paths": (C.c_int, [vp, C.POINTER(NavField3Cfg), vp, vp, vp, i32, i32, vp, vp, vp, vp]),
     "tsl_tsdf_nav_field3_paths_dev": (C.c_int, [vp, C.POINTER(NavField3Cfg), vp, vp, vp, i32, i32, vp, vp, vp, vp, vp]),
+    "tsl_tsdf_nav_boxes": (C.c_int, [vp, C.POINTER(NavCorridorCfg), vp, vp, i32, vp, vp]),
+    "tsl_tsdf_nav_boxes_dev": (C.c_int, [vp, C.POINTER(NavCorridorCfg), vp, vp, i32, vp, vp, vp]),
+    "tsl_tsdf_nav_corridor": (C.c_int, [vp, C.POINTER(NavCorridorCfg), vp, vp, vp, i32, i32, vp, vp, vp, vp, vp]),
+    "tsl_tsdf_nav_corridor_dev": (C.c_int, [vp, C.POINTER(NavCorridorCfg), vp, vp, vp, i32, i32, vp, vp, vp, vp, vp, vp]),
     "tsl_tsdf_nav_terrain": (C.c_int, [vp, C.POINTER(NavTerrainCfg), vp, vp, vp, vp, vp, vp, vp, vp, vp]),
     "tsl_tsdf_nav_terrain_dev": (C.c_int, [vp, C.POINTER(NavTerrainCfg), vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
     "tsl_tsdf_set_option": (C.c_int, [vp, C.c_char_p, C.c_int]),

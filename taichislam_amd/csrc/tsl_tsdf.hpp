@@ -233,6 +233,8 @@ void nav_field_release(tsl_tsdf* m);     // tsl_nav_field.hip: the 2-D solver's 
 struct NavTerrainState;                  // tsl_nav_terrain.hip: scratch and host staging of the terrain layers (allocated by the first call)
 void nav_terrain_release(tsl_tsdf* m);
 void nav_field3_release(tsl_tsdf* m);    // tsl_nav_field3.hip: the 3-D solver's instance
+struct NavCorridorState;                 // tsl_nav_corridor.hip: the bit volume, the per-cell boxes and the host staging of the corridors (allocated by the first call)
+void nav_corridor_release(tsl_tsdf* m);
 }  // namespace tsl
 
 #define TSL_ESDF_SLOTS 4
@@ -309,6 +311,7 @@ struct tsl_tsdf {
     tsl::NavFieldState* nav_field;       // tsl_nav_field.hip (allocated by the first call)
     tsl::NavTerrainState* nav_terrain;   // tsl_nav_terrain.hip (allocated by the first call)
     tsl::NavFieldState* nav_field3;      // tsl_nav_field3.hip (allocated by the first call)
+    tsl::NavCorridorState* nav_corridor; // tsl_nav_corridor.hip (allocated by the first call)
 };
 
 namespace tsl {

@@ -1240,6 +1240,144 @@ class DenseTSDF(BaseMap):
         return self._nav_paths_call("nav_paths3d", "nav_field3d", "[D, H, W]", _lib.NavField3Cfg, self.L.tsl_tsdf_nav_field3_paths,
                                     self.L.tsl_tsdf_nav_field3_paths_dev, 3, field_result, starts, max_len)
 
+    # ---- safe corridors: free boxes around cells and along paths (tsl_nav_corridor.hip) -----------------
+    def _nav_corridor_cost(self, who, cost, extent, free_below, device):
+        """the cost of nav_boxes / nav_corridor -> (array or tensor [D, H, W], on the device?, whether it had two axes, the filled NavCorridorCfg)"""
+        planes = False                                              # an int extent reaches along the leading axis only in a volume
+        if isinstance(cost, dict):
+            planes = "stride" not in cost                           # nav_grid / nav_terrain: planes; flight_volume: a volume
+            cost = cost["cost"]
+        on_dev = hasattr(cost, "is_cuda")
+        if on_dev or device:
+            torch = _torch()
+            ct = cost if on_dev else torch.from_numpy(np.ascontiguousarray(np.asarray(cost, dtype=np.uint8)))
+            if ct.dtype != torch.uint8:
+                raise ValueError(f"{who}: cost must be uint8")
+            cost = ct.to(torch.device(f"cuda:{self.device}")).contiguous()
+        else:
+            cost = np.asarray(cost)
+            if cost.dtype != np.uint8:
+                raise ValueError(f"{who}: cost must be uint8")
+            cost = np.ascontiguousarray(cost)
+        shape = tuple(cost.shape)
+        if len(shape) not in (2, 3):
+            raise ValueError(f"{who}: cost must be [H, W], [B, H, W] or [D, H, W]")
+        two = len(shape) == 2
+        if two:
+            cost = cost.reshape((1,) + shape)
+        if isinstance(extent, (int, np.integer)):
+            e = int(extent)
+            ext = (0, e, e) if (two or planes) else (e, e, e)
+        else:
+            ext = tuple(int(e) for e in extent)
+            if len(ext) != 3:
+                raise ValueError(f"{who}: extent must be an int or (e_k, e_i, e_j)")
+        cfg = _lib.NavCorridorCfg(*cost.shape)
+        cfg.free_below = int(free_below)
+        cfg.ext_k, cfg.ext_i, cfg.ext_j = ext
+        cfg.max_boxes = 1
+        return cost, (on_dev or bool(device)), two, cfg
+
+    def nav_boxes(self, cost, cells, free_below=253, extent=16, device=False):
+        """The free box around every cell of a list: an axis-aligned box of free cells that contains the cell, grown face by face in the fixed order -j, +j,
+        -i, +i, -k, +k until no face can move (include/taichislam_hip.h states the rule; it is the one box that order gives, not the largest free box).
+        cost: a uint8 array [H, W],
+        [B, H, W] or [D, H, W] (1 <= D, H, W <= 4096, at most 2^28 cells), the dict of nav_grid or nav_terrain (its cost plane is used) or the dict of
+        flight_volume: the map is not read.  A cell is free when cost < free_below (1 .. 255).  cells: [S, 3] = layer, row, col ([S, 2] = row, col with
+        an [H, W] cost).  extent: the most a box may reach from its cell, in cells, 0 .. 127: an int or (e_k, e_i, e_j); an int on a 2-D cost or on
+        the dict of nav_grid / nav_terrain means (0, e, e) -- the planes are independent.  Returns {"boxes": int16 [S, 6] = (k0, i0, j0, k1, i1, j1),
+        both ends inclusive, "flags": u8 [S]}: flag _lib.BOX_BLOCKED = 1 for a cell that is not free (the box is the cell), _lib.BOX_OUTSIDE = 2 for a
+        cell outside (the box is six times -1).  numpy in gives numpy out; torch device tensors in (or device=True) give tensors out, asynchronously,
+        ordered with torch.cuda.current_stream (tsl_tsdf_nav_boxes_dev); cells that are a device tensor are prepared on the device and not read by the
+        host (the call still waits where the handle's scratch has to grow: the first call and any larger one)."""
+        cost, on_dev, two, cfg = self._nav_corridor_cost("nav_boxes", cost, extent, free_below, device or _is_device_tensor(cells))
+        width_ok = (2, 3) if two else (3,)
+        bad_cells = ValueError("nav_boxes: cells must be [S, 3]" + (" or [S, 2]" if two else ""))
+        if _is_device_tensor(cells):
+            # cells already on a device stay there: clipped, widened and made int32 by torch on the current stream, so the call does not wait
+            torch = _torch()
+            if cells.dim() != 2 or cells.shape[1] not in width_ok:
+                raise bad_cells
+            c = cells.to(cost.device).clamp(-(1 << 31), (1 << 31) - 1).to(torch.int32)
+            if c.shape[1] == 2:
+                c = torch.cat([torch.zeros((c.shape[0], 1), dtype=torch.int32, device=c.device), c], 1)
+            c = c.contiguous()
+        else:
+            c = cells.numpy() if hasattr(cells, "is_cuda") else np.asarray(cells)
+            if c.size == 0:
+                c = np.zeros((0, 3), np.int32)
+            if c.ndim != 2 or c.shape[1] not in width_ok:
+                raise bad_cells
+            c = np.clip(c.astype(np.int64), -(1 << 31), (1 << 31) - 1).astype(np.int32)
+            if c.shape[1] == 2:
+                c = np.concatenate([np.zeros((c.shape[0], 1), np.int32), c], 1)
+            c = np.ascontiguousarray(c)
+        S = c.shape[0]
+        if on_dev:
+            torch = _torch()
+            dev = cost.device
+            boxes = torch.empty((S, 6), dtype=torch.int16, device=dev)
+            flags = torch.empty(S, dtype=torch.uint8, device=dev)
+            cd = (c if hasattr(c, "is_cuda") else torch.from_numpy(c).to(dev)) if S else None
+            _lib.check(self.L.tsl_tsdf_nav_boxes_dev(self.h, C.byref(cfg), cost.data_ptr(), cd.data_ptr() if S else None, S, boxes.data_ptr(), flags.data_ptr(),
+                                                     torch.cuda.current_stream(dev).cuda_stream))
+        else:
+            boxes, flags = np.empty((S, 6), np.int16), np.empty(S, np.uint8)
+            _lib.check(self.L.tsl_tsdf_nav_boxes(self.h, C.byref(cfg), _vp(cost), _vp(c) if S else None, S, _vp(boxes), _vp(flags)))
+        return {"boxes": boxes, "flags": flags}
+
+    def nav_corridor(self, cost, paths, free_below=253, extent=16, max_boxes=64, planes=None):
+        """The safe corridor of every path: a short chain of free boxes (nav_boxes) that contains the path, the form corridor-based trajectory optimisers
+        take.  cost, free_below and extent as in nav_boxes.  paths: the dict of nav_paths or nav_paths3d, or (cells, length) with cells [P, L, 3] or
+        [P, L, 2]; cells of width 2 get their plane from `planes` ([P], default 0) in front.  The walk: the first box is the box of the path's first
+        cell; the next box is seeded at the last path cell the current box still holds (the cell after the seed when it holds none further), until a
+        box holds the path's last cell (status 0) or max_boxes boxes (1 .. L) are out (status 1); an empty path has status 2.  Returns a dict: `boxes` int16
+        [P, max_boxes, 6], `seed` int32 [P, max_boxes] (the index of each box's cell in its path), `link` u8 [P, max_boxes] (0 the first box, 1 the box
+        shares a cell with the one before, 2 it shares none -- the two only touch --, plus 4 when its seed is not free or outside), `count` int32 [P],
+        `status` u8 [P], and `free_below` and `extent` (e_k, e_i, e_j).  Rows past count hold -1 (link 255).  Tensors in (the cost or the paths) give
+        tensors out, asynchronously on torch.cuda.current_stream (tsl_tsdf_nav_corridor_dev); otherwise numpy arrays."""
+        cells, length = (paths["cells"], paths["length"]) if isinstance(paths, dict) else paths
+        want_dev = hasattr(cells, "is_cuda") or hasattr(cost, "is_cuda") or (isinstance(cost, dict) and hasattr(cost["cost"], "is_cuda"))
+        cost, on_dev, two, cfg = self._nav_corridor_cost("nav_corridor", cost, extent, free_below, want_dev)
+        if len(cells.shape) != 3 or cells.shape[2] not in (2, 3):
+            raise ValueError("nav_corridor: cells must be [P, L, 3] or [P, L, 2]")
+        P, L, width = (int(v) for v in cells.shape)
+        if tuple(length.shape) != (P,):
+            raise ValueError("nav_corridor: length must be [P]")
+        Q = int(max_boxes)
+        cfg.max_boxes = Q
+        if on_dev:
+            torch = _torch()
+            dev = cost.device
+            as_t = lambda a, dt: (a if hasattr(a, "is_cuda") else torch.from_numpy(np.ascontiguousarray(np.asarray(a)))).to(device=dev, dtype=dt)
+            cd, ld = as_t(cells, torch.int16), as_t(length, torch.int32).contiguous()
+            if width == 2:
+                pl = torch.zeros(P, dtype=torch.int16, device=dev) if planes is None else as_t(planes, torch.int16).reshape(P)
+                cd = torch.cat([pl[:, None, None].expand(P, L, 1), cd], 2)
+            cd = cd.contiguous()
+            Qc = max(Q, 0)
+            boxes = torch.empty((P, Qc, 6), dtype=torch.int16, device=dev)
+            seed = torch.empty((P, Qc), dtype=torch.int32, device=dev)
+            link = torch.empty((P, Qc), dtype=torch.uint8, device=dev)
+            count = torch.empty(P, dtype=torch.int32, device=dev)
+            status = torch.empty(P, dtype=torch.uint8, device=dev)
+            ptr = lambda t: t.data_ptr() if P else None
+            _lib.check(self.L.tsl_tsdf_nav_corridor_dev(self.h, C.byref(cfg), cost.data_ptr(), ptr(cd), ptr(ld), P, L, boxes.data_ptr(), seed.data_ptr(),
+                                                        link.data_ptr(), count.data_ptr(), status.data_ptr(), torch.cuda.current_stream(dev).cuda_stream))
+        else:
+            cd, ld = np.asarray(cells, dtype=np.int16), np.ascontiguousarray(np.asarray(length, dtype=np.int32))
+            if width == 2:
+                pl = np.zeros(P, np.int16) if planes is None else np.asarray(planes, dtype=np.int16).reshape(P)
+                cd = np.concatenate([np.broadcast_to(pl[:, None, None], (P, L, 1)), cd], 2)
+            cd = np.ascontiguousarray(cd)
+            Qc = max(Q, 0)
+            boxes, seed, link = np.empty((P, Qc, 6), np.int16), np.empty((P, Qc), np.int32), np.empty((P, Qc), np.uint8)
+            count, status = np.empty(P, np.int32), np.empty(P, np.uint8)
+            _lib.check(self.L.tsl_tsdf_nav_corridor(self.h, C.byref(cfg), _vp(cost), _vp(cd) if P else None, _vp(ld) if P else None, P, L, _vp(boxes), _vp(seed),
+                                                    _vp(link), _vp(count), _vp(status)))
+        return {"boxes": boxes, "seed": seed, "link": link, "count": count, "status": status, "free_below": int(free_below),
+                "extent": (int(cfg.ext_k), int(cfg.ext_i), int(cfg.ext_j))}
+
     def flight_volume(self, stride=4, z_range=None, lut=None, cost_unknown=255, cost_outside=255, refresh=True, device=False):
         """The cost volume of nav_field3d from the ESDF: a lattice of one sample per cell of `stride`^3 voxels, through query_esdf(interpolate=False)
         and utils.nav.distance_cost -- no kernel of its own.  Cell (k, i, j) is sampled at the centre of the voxel origin + (k, i, j) * stride +

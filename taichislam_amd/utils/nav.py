@@ -149,3 +149,33 @@ def frontier_reach3d(frontiers, field_result, volume):
     cj = (idx[:, 1] + half[2] - org[2]) // s
     ok = (ck >= 0) & (ck < f.shape[0]) & (ci >= 0) & (ci < f.shape[1]) & (cj >= 0) & (cj < f.shape[2])
     return _cluster_least(frontiers, f, ok, (ck, ci, cj))
+
+
+# ---- safe corridors: the boxes of DenseTSDF.nav_boxes / nav_corridor in metres ---------------------------------------------
+def corridor_metres(boxes, volume=None, N=None, voxel=None):
+    """The boxes of DenseTSDF.nav_boxes / nav_corridor as metric boxes in the frame of query_esdf: float64 [..., 2, 3], the lower and the upper corner
+    (x, y, z) of the union of the voxels of the box's cells.  boxes: [..., 6] = (k0, i0, j0, k1, i1, j1); a voxel of signed index n spans (n - 1/2) *
+    voxel .. (n + 1/2) * voxel, its centre being where flight_volume places its samples.  volume: the dict of DenseTSDF.flight_volume -- cell n of an
+    axis covers the signed voxel indices n * stride + origin - half .. + stride - 1 (layer -> z, row -> x, column -> y).  Without a volume the boxes
+    are those of 2-D planes of the map (nav_grid, nav_terrain): N (the map's cells along x and y) and voxel give x and y, one voxel per cell, and z is
+    NaN -- the plane's height range is the band's, which the boxes do not carry.  Rows of -1 (a seed outside, the rows past `count`) give NaN.  Host
+    numpy; tensors are copied."""
+    b = _host(boxes).astype(np.int64)
+    if b.ndim < 1 or b.shape[-1] != 6:
+        raise ValueError("corridor_metres: boxes must be [..., 6]")
+    if volume is not None:
+        s, vs = int(volume["stride"]), float(volume["voxel"])
+        off = [int(o) - int(h) for o, h in zip(volume["origin"], volume["half"])]      # per (layer, row, col)
+    else:
+        if N is None or voxel is None:
+            raise ValueError("corridor_metres: needs the dict of flight_volume, or N and voxel")
+        s, vs = 1, float(voxel)
+        off = [0, -(int(N) // 2), -(int(N) // 2)]
+    out = np.empty(b.shape[:-1] + (2, 3), np.float64)
+    for x, a in enumerate((1, 2, 0)):                               # x from the row, y from the column, z from the layer
+        out[..., 0, x] = (b[..., a] * s + off[a] - 0.5) * vs
+        out[..., 1, x] = (b[..., a + 3] * s + off[a] + s - 0.5) * vs
+    if volume is None:
+        out[..., 2] = np.nan
+    out[(b < 0).any(-1)] = np.nan
+    return out
