@@ -841,6 +841,61 @@ int  tsl_tsdf_nav_corridor(tsl_tsdf* m, const tsl_nav_corridor_cfg* cfg, const u
 int  tsl_tsdf_nav_corridor_dev(tsl_tsdf* m, const tsl_nav_corridor_cfg* cfg, const void* cost_dev, const void* cells_dev, const void* length_dev, int32_t P, int32_t L,
                                void* boxes_dev, void* seed_dev, void* link_dev, void* count_dev, void* status_dev, void* user_stream);
 
+/* ---- free-space topology graph (tsl_topo.hip): the ray and facelet work of TopoGraphGen (taichi_slam/mapping/topo_graph.py).  A
+ * tsl_topo is bound to one tsl_tsdf, reads it and never writes it, and owns two device stores that grow on demand: the facelets (structure of arrays: the three
+ * vertices, v0, edge1, edge2, normal, centre, poly = the node that made it; at most max_facelets) and the nodes (centre, facelet range; at most 4096, the
+ * reference's max_map_node).  The hull (scipy's Qhull), the region growing, the frontiers and the loop stay with the caller (mapping/topo_graph.py).
+ *
+ * DEFINITION.  The reference's top-level loops are parallel, so its black-list order, its centre sum and its neighbour list are whatever the atomics gave
+ * (and neighbor_node_ids, coll_det_num slots for up to 2 * coll_det_num - 4 facelets, can overflow).  This back end defines the SEQUENTIAL reading: every loop
+ * of topo_graph.py in ascending index order, all arithmetic f32 in the order the source writes it, no contraction, correctly rounded divide and sqrt.
+ *   normalising   v.normalized() = v / sqrt(x * x + y * y + z * z): the sum left to right, the division per component.  cross(a, b) = (a1 b2 - a2 b1,
+ *                 a2 b0 - a0 b2, a0 b1 - a1 b0), dot(a, b) = (a0 b0 + a1 b1) + a2 b2.
+ *   facelet       (:36-50) edge1 = v1 - v0, edge2 = v2 - v0, centre = ((v0 + v1) + v2) / 3, normal = cross(edge1, edge2).normalized(), negated when its dot with
+ *                 (((v0 + v1) + v2) - 3 * start).normalized() is < 0.
+ *   ray/triangle  (:52-70) as written; |a| > 1e-5f or no hit; b2 = (1 - b0) - b1.  A NaN t fails every comparison and never wins.
+ *   collision     (:472-488) over the nodes k != skip_idx with norm(pos - centre_k) < max_dist + max_raycast_dist (one f32 add) the least t with
+ *                 backward < t < max_dist; among equal t the lowest facelet index (what the sequential strict `<` keeps).  Without a hit t = max_dist and
+ *                 poly = -1.  The position is pos + dir * t.
+ *   combined ray  (:490-507) the collision with backward = -0.01f, then the map walk of tsl_tsdf_query_raycast to max_dist -- to the facelet hit's t if there
+ *                 was one; (int)(t / voxel) steps, none for a t below one voxel -- bit for bit, its rule for positions that are not finite or have no int
+ *                 cell and its len and end_xyz on a miss included.  The map wins (type 0) only without a facelet hit or when it hit and len_map < t,
+ *                 strictly; otherwise type 1.  poly is the facelet hit's node even when the map wins.  A NaN component of a position leaves as 0x7fc00000.
+ *   collide       (:444-470) rays 0 .. coll_det_num - 1 from one start, blacks (hits) and whites compacted in ray order, node_size = the left-to-right f32 sum
+ *                 of the black lengths / their count; succ = !(no black || (no white && node_size < thres_size)).
+ *   add_poly      (:380-405) facelets in ascending order into the store, poly = the new node's index; per facelet (:324-342; is_near_pos_occupy(centre, 0)
+ *                 has an empty loop and is false) reason 1: is_pos_unobserved(centre), else 2: is_pos_occupy(centre + normal * voxel), else 3: the combined ray
+ *                 from there along the normal to max_dist hit; is_frontier = reason 0; neigh = that ray's poly when it hit with type 1, else -1.  The rays see
+ *                 the nodes made before this one.  The node centre is the left-to-right f32 sum of (v0 + v1) + v2 over the facelets, divided by 3 * nf.
+ * TSL_ERR_ARG, before anything is launched or written (the text names the entry point): a null handle or argument; coll_det_num outside 4 .. 512 (the
+ * reference's region queue holds 1024 facelets); max_facelets outside 1 .. 2^24; a max_dist or max_raycast_dist that is negative, not finite or above 2^20
+ * voxels; a NaN backward; n outside 0 .. 2^20; nf outside 1 .. 4096; a flag other than bit 0; a handle whose map was destroyed (tsl_topo_destroy is still
+ * fine).  TSL_ERR_CAPACITY, with nothing changed: the facelet store would pass max_facelets, or 4096 nodes exist. */
+typedef struct tsl_topo tsl_topo;
+int  tsl_topo_create(tsl_tsdf* m, int32_t coll_det_num, float max_raycast_dist, int64_t max_facelets, tsl_topo** out);
+void tsl_topo_destroy(tsl_topo* t);
+int  tsl_topo_reset(tsl_topo* t);                       /* both stores empty; their memory stays */
+int  tsl_topo_counts(tsl_topo* t, int64_t* n_facelets, int32_t* n_nodes);
+/* n rays: flags bit 0 = facelets only (the collision alone, type 1; verify_frontier's second cast); skip_idx int32 [n] or NULL = -1.  Outputs (any may be NULL):
+ * hit u8, type u8 (0 map, 1 facelet), end_xyz f32 [n][3], len f32, poly int32. */
+int  tsl_topo_rays(tsl_topo* t, const float* pos, const float* dir, const int32_t* skip_idx, int64_t n, float max_dist, float backward, int32_t flags, uint8_t* hit,
+                   uint8_t* type, float* end_xyz, float* len, int32_t* poly);
+/* the same with DEVICE buffers (no output may be NULL), ordered with `user_stream` like tsl_tsdf_query_raycast_dev; nothing is waited for */
+int  tsl_topo_rays_dev(tsl_topo* t, const void* pos_dev, const void* dir_dev, const void* skip_idx_dev, int64_t n, float max_dist, float backward, int32_t flags,
+                       void* hit_dev, void* type_dev, void* end_xyz_dev, void* len_dev, void* poly_dev, void* user_stream);
+/* the coll_det_num rays of one expansion: start f32 [3], dirs f32 [coll_det_num][3]; black_pos / black_dir f32 [coll_det_num][3], black_len f32 [coll_det_num],
+ * white_pos likewise (may be NULL, as white_num and node_size) */
+int  tsl_topo_collide(tsl_topo* t, const float* start, const float* dirs, float thres_size, int32_t* succ, int32_t* black_num, float* black_pos, float* black_dir,
+                      float* black_len, int32_t* white_num, float* white_pos, float* node_size);
+/* one node from nf triangles f32 [nf][3][3]; outputs (any may be NULL): is_frontier u8 [nf], reason u8 [nf], neigh int32 [nf], centre f32 [3], the node's index */
+int  tsl_topo_add_poly(tsl_topo* t, const float* tris, int32_t nf, const float* start, float max_dist, uint8_t* is_frontier, uint8_t* reason, int32_t* neigh,
+                       float* centre, int32_t* node_idx);
+/* DEVICE pointers of the store (tri_vertices f32 [.][3][3], normal and centre f32 [.][3], poly int32) and the counts; the pointers change when the store grows */
+int  tsl_topo_buffers_dev(tsl_topo* t, void** tri_vertices_dev, void** normal_dev, void** centre_dev, void** poly_dev, int64_t* n_facelets, int32_t* n_nodes);
+/* facelets first .. first + n - 1 of the store to host arrays (any may be NULL) */
+int  tsl_topo_read_facelets(tsl_topo* t, int64_t first, int64_t n, float* tri_vertices, float* v0, float* edge1, float* edge2, float* normal, float* centre,
+                            int32_t* poly);
+
 /* ---- terrain layers for ground robots (tsl_nav_terrain.hip): per height band and (x, y) column the height of the surface a robot
  * can stand on, over the robot's footprint the step and the slope of that surface, and a class, a distance and a cost in the vocabulary of
  * tsl_tsdf_nav_grid, so that tsl_tsdf_nav_field and the OccupancyGrid adapters take them unchanged.  Where nav_grid calls a column an obstacle as soon as

@@ -346,6 +346,16 @@ SIGNATURES = {
     "tsl_tsdf_nav_corridor_dev": (C.c_int, [vp, C.POINTER(NavCorridorCfg), vp, vp, vp, i32, i32, vp, vp, vp, vp, vp, vp]),
     "tsl_tsdf_nav_terrain": (C.c_int, [vp, C.POINTER(NavTerrainCfg), vp, vp, vp, vp, vp, vp, vp, vp, vp]),
     "tsl_tsdf_nav_terrain_dev": (C.c_int, [vp, C.POINTER(NavTerrainCfg), vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
+    "tsl_topo_create": (C.c_int, [vp, i32, f32, i64, C.POINTER(vp)]),
+    "tsl_topo_destroy": (None, [vp]),
+    "tsl_topo_reset": (C.c_int, [vp]),
+    "tsl_topo_counts": (C.c_int, [vp, pi64, pi32]),
+    "tsl_topo_rays": (C.c_int, [vp, vp, vp, vp, i64, f32, f32, i32, vp, vp, vp, vp, vp]),
+    "tsl_topo_rays_dev": (C.c_int, [vp, vp, vp, vp, i64, f32, f32, i32, vp, vp, vp, vp, vp, vp]),
+    "tsl_topo_collide": (C.c_int, [vp, vp, vp, f32, pi32, pi32, vp, vp, vp, pi32, vp, C.POINTER(C.c_float)]),
+    "tsl_topo_add_poly": (C.c_int, [vp, vp, i32, vp, f32, vp, vp, vp, vp, pi32]),
+    "tsl_topo_buffers_dev": (C.c_int, [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), pi64, pi32]),
+    "tsl_topo_read_facelets": (C.c_int, [vp, i64, i64, vp, vp, vp, vp, vp, vp, vp]),
     "tsl_tsdf_set_option": (C.c_int, [vp, C.c_char_p, C.c_int]),
     "tsl_tsdf_get_option": (C.c_int, [vp, C.c_char_p, C.POINTER(C.c_int)]),
     "tsl_tsdf_prof_enable": (C.c_int, [vp, C.c_int]),

@@ -2,24 +2,10 @@
 // is_pos_occupy / is_near_pos_occupy / is_pos_unobserved (taichi_slam/mapping/mapping_common.py:165-204) and
 // DenseTSDF.is_occupy / is_unobserved (dense_tsdf.py:148-155), reference root; TopoGraphGen calls them 64-128 rays at a
 // time (topo_graph.py:444-507).  One thread per query, read-only gathers through the brick table.
-#include "tsl_tsdf.hpp"
+#include "tsl_query.hpp"
 #include <cfloat>
 
 namespace tsl {
-
-__device__ __forceinline__ void q_read(const MapDev& M, int s, int i, int j, int k, float* tsdf, int* obs)
-{
-    *tsdf = 0.0f; *obs = 0;                                   // outside the volume / inactive cell reads as 0 (A7)
-    if (!in_volume(M, i, j, k)) return;
-    int l; const int b = brick_of(M, i, j, k, &l);
-    const int p = pool_lookup_ro(M, s, b);
-    if (p < 0) return;
-    const size_t v = (size_t)p * TSL_BRK3 + l;
-    *tsdf = h2f((h16)(M.tw[v] & 0xffffu)); *obs = M.obs[v];
-}
-// is_occupy  dense_tsdf.py:153-155 (an unobserved voxel reads TSDF = 0 and therefore counts as occupied)
-__device__ __forceinline__ bool q_occupied(const MapDev& M, int s, int i, int j, int k, float thres)
-{ float t; int o; q_read(M, s, i, j, k, &t, &o); return t < thres; }
 
 // mode 0: is_pos_occupy  1: is_pos_unobserved  2: is_near_pos_occupy(param)
 __global__ void __launch_bounds__(256) k_query_points(MapDev M, int s, float vs, float thres, int mode, int param, const float* __restrict__ xyz, long long n, uint8_t* out)

@@ -235,6 +235,7 @@ void nav_terrain_release(tsl_tsdf* m);
 void nav_field3_release(tsl_tsdf* m);    // tsl_nav_field3.hip: the 3-D solver's instance
 struct NavCorridorState;                 // tsl_nav_corridor.hip: the bit volume, the per-cell boxes and the host staging of the corridors (allocated by the first call)
 void nav_corridor_release(tsl_tsdf* m);
+void topo_map_gone(tsl_tsdf* m);         // tsl_topo.hip: the topology graphs bound to this map refuse every call from now on
 }  // namespace tsl
 
 #define TSL_ESDF_SLOTS 4

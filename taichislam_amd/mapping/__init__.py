@@ -4,3 +4,4 @@ from .dense_tsdf import DenseTSDF, depth_to_mm, frontier_view_candidates  # noqa
 from .taichi_octomap import Octomap  # noqa: F401
 from .marching_cube_mesher import MarchingCubeMesher  # noqa: F401
 from .submap_mapping import SubmapMapping  # noqa: F401
+from .topo_graph import TopoGraphGen  # noqa: F401
