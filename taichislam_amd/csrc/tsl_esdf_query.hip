@@ -8,6 +8,7 @@
 // tests/esdf_query_ref.py can restate it bit for bit in numpy.  Status per query: 0 ok, 1 a needed voxel is unknown, 2 a needed voxel is
 // outside the volume (or a coordinate is not finite); | 0x80 when the values come from an update that stopped before converging.
 #include "tsl_esdf_sample.hpp"      // esdf_sample: the look-up, the value and the interpolant, shared with tsl_path_score.hip
+#include "tsl_stage.hpp"
 
 namespace tsl {
 
@@ -72,17 +73,13 @@ int tsl_esdf_query_points(tsl_tsdf* m, int mode, float unknown_value, const floa
     if (n == 0) return TSL_OK;
     TSL_HIP(hipSetDevice(m->device));
     if ((rc = esdf_finish(m))) return rc;                      // the values handed out are the fixed point of the last update
-    const size_t c = (size_t)n, o_d = c * 12, o_g = o_d + c * 4, o_s = o_g + (grad ? c * 12 : 0);
-    if ((rc = grow(&m->xbuf, &m->xbuf_bytes, o_s + c + 64))) return rc;
-    char* base = (char*)m->xbuf;
-    TSL_HIP(hipMemcpy(base, xyz, c * 12, hipMemcpyHostToDevice));
     const hipStream_t q = ms(m);
-    if ((rc = esdf_query_launch(m, q, mode, unknown_value, (const float*)base, n, (float*)(base + o_d), grad ? (float*)(base + o_g) : nullptr, (uint8_t*)(base + o_s)))) return rc;
-    TSL_HIP(hipStreamSynchronize(q));
-    TSL_HIP(hipMemcpy(dist, base + o_d, c * 4, hipMemcpyDeviceToHost));
-    if (grad) TSL_HIP(hipMemcpy(grad, base + o_g, c * 12, hipMemcpyDeviceToHost));
-    TSL_HIP(hipMemcpy(status, base + o_s, c, hipMemcpyDeviceToHost));
-    return TSL_OK;
+    const size_t c = (size_t)n;
+    Stage st(&m->xbuf, &m->xbuf_bytes, q);
+    const int i_x = st.in(xyz, c * 12), i_d = st.out(dist, c * 4), i_g = st.out(grad, c * 12), i_s = st.out(status, c);
+    if ((rc = st.upload())) return rc;
+    if ((rc = esdf_query_launch(m, q, mode, unknown_value, st.ptr<const float>(i_x), n, st.ptr<float>(i_d), st.ptr<float>(i_g), st.ptr<uint8_t>(i_s)))) return rc;
+    return st.download();
 }
 
 int tsl_esdf_query_points_dev(tsl_tsdf* m, int mode, float unknown_value, const void* xyz_dev, int64_t n, void* dist_dev, void* grad_dev, void* status_dev, void* user_stream)

@@ -24,7 +24,7 @@
 //   k_nc_chain       one wave per path over the per-cell boxes: 64 cells per ballot of "outside the box", the lowest set bit is the first cell outside.
 // No atomics, no LDS, no workgroup waits for another, and every loop has a bound known at launch (ext, L, max_boxes).
 #include <string>
-#include "tsl_tsdf.hpp"
+#include "tsl_stage.hpp"
 
 namespace tsl {
 
@@ -40,8 +40,8 @@ typedef unsigned long long nc_word;
 
 struct NcCfg { int D, H, W, pitch, free_below, ek, ei, ej, Q; };
 
-// the scratch of a handle: the bit volume, the per-cell boxes of the corridor form, and the device copies of the host forms' arguments and results
-enum { NC_BITS, NC_CBOX, NC_CFLAG, NC_COST, NC_CELLS, NC_LEN, NC_BOXES, NC_FLAGS, NC_SEED, NC_LINK, NC_COUNT, NC_STATUS, NC_NBUF };
+// the scratch of a handle: the bit volume and the per-cell boxes and flags of the corridor form
+enum { NC_BITS, NC_CBOX, NC_CFLAG, NC_NBUF };
 struct NavCorridorState { void* p[NC_NBUF]; size_t b[NC_NBUF]; };
 
 // ---- pack ------------------------------------------------------------------------------------------------------------------------------------
@@ -361,20 +361,13 @@ int tsl_tsdf_nav_boxes(tsl_tsdf* m, const tsl_nav_corridor_cfg* cfg, const uint8
     TSL_HIP(hipSetDevice(m->device));
     const hipStream_t q = ms(m);
     if ((rc = nc_state(m))) return rc;
-    NavCorridorState* S = m->nav_corridor;
-    const size_t ncells = (size_t)C.D * C.H * C.W, N = (size_t)n;
-    NC_GROW(NC_COST, ncells);
-    NC_GROW(NC_CELLS, N * 3 * sizeof(int32_t));
-    NC_GROW(NC_BOXES, N * 6 * sizeof(int16_t));
-    NC_GROW(NC_FLAGS, N);
-    TSL_HIP(hipMemcpyAsync(S->p[NC_COST], cost, ncells, hipMemcpyHostToDevice, q));
-    TSL_HIP(hipMemcpyAsync(S->p[NC_CELLS], cells, N * 3 * sizeof(int32_t), hipMemcpyHostToDevice, q));
-    if ((rc = nc_boxes_launch(m, q, C, (const uint8_t*)S->p[NC_COST], (const int32_t*)S->p[NC_CELLS], n, (int16_t*)S->p[NC_BOXES], (uint8_t*)S->p[NC_FLAGS])))
-        return rc;
-    TSL_HIP(hipStreamSynchronize(q));
-    if (boxes) TSL_HIP(hipMemcpy(boxes, S->p[NC_BOXES], N * 6 * sizeof(int16_t), hipMemcpyDeviceToHost));
-    if (flags) TSL_HIP(hipMemcpy(flags, S->p[NC_FLAGS], N, hipMemcpyDeviceToHost));
-    return TSL_OK;
+    const size_t N = (size_t)n;
+    Stage st(&m->xbuf, &m->xbuf_bytes, q);
+    const int i_cost = st.in(cost, (size_t)C.D * C.H * C.W), i_cells = st.in(cells, N * 3 * sizeof(int32_t)), i_boxes = st.out(boxes, N * 6 * sizeof(int16_t)),
+              i_flags = st.out(flags, N);
+    if ((rc = st.upload())) return rc;
+    if ((rc = nc_boxes_launch(m, q, C, st.ptr<const uint8_t>(i_cost), st.ptr<const int32_t>(i_cells), n, st.ptr<int16_t>(i_boxes), st.ptr<uint8_t>(i_flags)))) return rc;
+    return st.download();
 }
 
 int tsl_tsdf_nav_boxes_dev(tsl_tsdf* m, const tsl_nav_corridor_cfg* cfg, const void* cost_dev, const void* cells_dev, int32_t n, void* boxes_dev, void* flags_dev,
@@ -400,28 +393,15 @@ int tsl_tsdf_nav_corridor(tsl_tsdf* m, const tsl_nav_corridor_cfg* cfg, const ui
     TSL_HIP(hipSetDevice(m->device));
     const hipStream_t q = ms(m);
     if ((rc = nc_state(m))) return rc;
-    NavCorridorState* S = m->nav_corridor;
-    const size_t ncells = (size_t)C.D * C.H * C.W, np = (size_t)P, nq = np * C.Q;
-    NC_GROW(NC_COST, ncells);
-    NC_GROW(NC_CELLS, np * L * 3 * sizeof(int16_t));
-    NC_GROW(NC_LEN, np * sizeof(int32_t));
-    NC_GROW(NC_BOXES, nq * 6 * sizeof(int16_t));
-    NC_GROW(NC_SEED, nq * sizeof(int32_t));
-    NC_GROW(NC_LINK, nq);
-    NC_GROW(NC_COUNT, np * sizeof(int32_t));
-    NC_GROW(NC_STATUS, np);
-    TSL_HIP(hipMemcpyAsync(S->p[NC_COST], cost, ncells, hipMemcpyHostToDevice, q));
-    TSL_HIP(hipMemcpyAsync(S->p[NC_CELLS], cells, np * L * 3 * sizeof(int16_t), hipMemcpyHostToDevice, q));
-    TSL_HIP(hipMemcpyAsync(S->p[NC_LEN], length, np * sizeof(int32_t), hipMemcpyHostToDevice, q));
-    if ((rc = nc_corridor_launch(m, q, C, (const uint8_t*)S->p[NC_COST], (const int16_t*)S->p[NC_CELLS], (const int32_t*)S->p[NC_LEN], P, L, (int16_t*)S->p[NC_BOXES],
-                                 (int32_t*)S->p[NC_SEED], (uint8_t*)S->p[NC_LINK], (int32_t*)S->p[NC_COUNT], (uint8_t*)S->p[NC_STATUS]))) return rc;
-    TSL_HIP(hipStreamSynchronize(q));
-    if (boxes) TSL_HIP(hipMemcpy(boxes, S->p[NC_BOXES], nq * 6 * sizeof(int16_t), hipMemcpyDeviceToHost));
-    if (seed) TSL_HIP(hipMemcpy(seed, S->p[NC_SEED], nq * sizeof(int32_t), hipMemcpyDeviceToHost));
-    if (link) TSL_HIP(hipMemcpy(link, S->p[NC_LINK], nq, hipMemcpyDeviceToHost));
-    if (count) TSL_HIP(hipMemcpy(count, S->p[NC_COUNT], np * sizeof(int32_t), hipMemcpyDeviceToHost));
-    if (status) TSL_HIP(hipMemcpy(status, S->p[NC_STATUS], np, hipMemcpyDeviceToHost));
-    return TSL_OK;
+    const size_t np = (size_t)P, nq = np * C.Q;
+    Stage st(&m->xbuf, &m->xbuf_bytes, q);
+    const int i_cost = st.in(cost, (size_t)C.D * C.H * C.W), i_cells = st.in(cells, np * L * 3 * sizeof(int16_t)), i_len = st.in(length, np * sizeof(int32_t)),
+              i_boxes = st.out(boxes, nq * 6 * sizeof(int16_t)), i_seed = st.out(seed, nq * sizeof(int32_t)), i_link = st.out(link, nq),
+              i_count = st.out(count, np * sizeof(int32_t)), i_status = st.out(status, np);
+    if ((rc = st.upload())) return rc;
+    if ((rc = nc_corridor_launch(m, q, C, st.ptr<const uint8_t>(i_cost), st.ptr<const int16_t>(i_cells), st.ptr<const int32_t>(i_len), P, L, st.ptr<int16_t>(i_boxes),
+                                 st.ptr<int32_t>(i_seed), st.ptr<uint8_t>(i_link), st.ptr<int32_t>(i_count), st.ptr<uint8_t>(i_status)))) return rc;
+    return st.download();
 }
 
 int tsl_tsdf_nav_corridor_dev(tsl_tsdf* m, const tsl_nav_corridor_cfg* cfg, const void* cost_dev, const void* cells_dev, const void* length_dev, int32_t P, int32_t L,

@@ -23,7 +23,7 @@
 #pragma once
 #include <cstring>
 #include <string>
-#include "tsl_tsdf.hpp"
+#include "tsl_stage.hpp"
 
 namespace tsl {
 
@@ -38,9 +38,9 @@ struct NfCfg { int D, H, W, neutral, lethal, nz, tx, ty, tz, max_rounds, rounds_
 struct NfCtl { uint32_t marks[2]; int32_t rounds, n_bad; unsigned long long visits; };
 
 struct NavFieldState {
-    void *cost, *seeds, *field, *parent, *act, *ctl, *stats, *starts, *cells, *plen, *pstatus, *pcost;
-    size_t b_cost, b_seeds, b_field, b_parent, b_act, b_ctl, b_stats, b_starts, b_cells, b_plen, b_pstatus, b_pcost;
-    uint32_t* pin;                 // pinned: the count the host reads between rounds, and the statistics on their way back
+    void *act, *ctl, *stats;       // the activity maps, the control block, the statistics of a call that asks for none
+    size_t b_act, b_ctl, b_stats;
+    uint32_t* pin;                 // pinned: the count the host reads between rounds
 };
 
 __device__ __forceinline__ uint32_t nf_add(uint32_t a, uint32_t c)      // a + c clipped to NF_MAXV; unreached stays unreached
@@ -147,7 +147,7 @@ inline void nf_release(NavFieldState** slot)
 {
     NavFieldState* S = *slot;
     if (!S) return;
-    void* ptrs[] = { S->cost, S->seeds, S->field, S->parent, S->act, S->ctl, S->stats, S->starts, S->cells, S->plen, S->pstatus, S->pcost };
+    void* ptrs[] = { S->act, S->ctl, S->stats };
     for (void* p : ptrs) if (p) (void)hipFree(p);
     if (S->pin) (void)hipHostFree(S->pin);
     delete S;
@@ -281,23 +281,14 @@ int nf_field_host(tsl_tsdf* m, const typename T::cfg_t* cfg, const uint8_t* cost
     TSL_HIP(hipSetDevice(m->device));
     const hipStream_t q = ms(m);
     if ((rc = nf_state(&T::state(m), T::name))) return rc;
-    NavFieldState* S = T::state(m);
     const size_t cells = (size_t)C.D * C.H * C.W;
-    NF_GROW(cost, b_cost, cells);
-    NF_GROW(field, b_field, cells * sizeof(uint32_t));
-    if (parent) NF_GROW(parent, b_parent, cells);
-    if (n_seeds > 0) NF_GROW(seeds, b_seeds, (size_t)n_seeds * 4 * sizeof(int32_t));
-    NF_GROW(stats, b_stats, sizeof(stats_t));
-    TSL_HIP(hipMemcpyAsync(S->cost, cost, cells, hipMemcpyHostToDevice, q));
-    if (n_seeds > 0) TSL_HIP(hipMemcpyAsync(S->seeds, seeds, (size_t)n_seeds * 4 * sizeof(int32_t), hipMemcpyHostToDevice, q));
-    if ((rc = nf_launch<T>(m, q, C, (const uint8_t*)S->cost, (const int32_t*)S->seeds, n_seeds, (uint32_t*)S->field, parent ? (uint8_t*)S->parent : nullptr,
-                           (stats_t*)S->stats))) return rc;
-    TSL_HIP(hipMemcpyAsync(S->pin + 4, S->stats, sizeof(stats_t), hipMemcpyDeviceToHost, q));
-    TSL_HIP(hipStreamSynchronize(q));
-    TSL_HIP(hipMemcpy(field, S->field, cells * sizeof(uint32_t), hipMemcpyDeviceToHost));
-    if (parent) TSL_HIP(hipMemcpy(parent, S->parent, cells, hipMemcpyDeviceToHost));
-    if (stats) memcpy(stats, S->pin + 4, sizeof(stats_t));
-    return TSL_OK;
+    Stage st(&m->xbuf, &m->xbuf_bytes, q);
+    const int i_cost = st.in(cost, cells), i_seeds = st.in(seeds, (size_t)(n_seeds > 0 ? n_seeds : 0) * 4 * sizeof(int32_t)),
+              i_field = st.out(field, cells * sizeof(uint32_t)), i_parent = st.out(parent, cells), i_stats = st.out(stats, sizeof(stats_t));
+    if ((rc = st.upload())) return rc;
+    if ((rc = nf_launch<T>(m, q, C, st.ptr<const uint8_t>(i_cost), st.ptr<const int32_t>(i_seeds), n_seeds, st.ptr<uint32_t>(i_field), st.ptr<uint8_t>(i_parent),
+                           st.ptr<stats_t>(i_stats)))) return rc;
+    return st.download();
 }
 
 // device pointers: ordered with the caller's stream
@@ -325,27 +316,15 @@ int nf_paths_host(tsl_tsdf* m, const typename T::cfg_t* cfg, const uint32_t* fie
     if (n_starts == 0) return TSL_OK;
     TSL_HIP(hipSetDevice(m->device));
     const hipStream_t q = ms(m);
-    if ((rc = nf_state(&T::state(m), T::name))) return rc;
-    NavFieldState* S = T::state(m);
     const size_t ncells = (size_t)C.D * C.H * C.W, P = (size_t)n_starts, L = (size_t)max_len;
-    NF_GROW(field, b_field, ncells * sizeof(uint32_t));
-    NF_GROW(parent, b_parent, ncells);
-    NF_GROW(starts, b_starts, P * 3 * sizeof(int32_t));
-    NF_GROW(cells, b_cells, P * L * T::NCOMP * sizeof(int16_t));
-    NF_GROW(plen, b_plen, P * sizeof(int32_t));
-    NF_GROW(pstatus, b_pstatus, P);
-    NF_GROW(pcost, b_pcost, P * sizeof(uint32_t));
-    TSL_HIP(hipMemcpyAsync(S->field, field, ncells * sizeof(uint32_t), hipMemcpyHostToDevice, q));
-    TSL_HIP(hipMemcpyAsync(S->parent, parent, ncells, hipMemcpyHostToDevice, q));
-    TSL_HIP(hipMemcpyAsync(S->starts, starts, P * 3 * sizeof(int32_t), hipMemcpyHostToDevice, q));
-    if ((rc = nf_paths_launch<T>(m, q, C, (const uint32_t*)S->field, (const uint8_t*)S->parent, (const int32_t*)S->starts, n_starts, max_len, (int16_t*)S->cells,
-                                 (int32_t*)S->plen, (uint8_t*)S->pstatus, (uint32_t*)S->pcost))) return rc;
-    TSL_HIP(hipStreamSynchronize(q));
-    if (cells) TSL_HIP(hipMemcpy(cells, S->cells, P * L * T::NCOMP * sizeof(int16_t), hipMemcpyDeviceToHost));
-    if (length) TSL_HIP(hipMemcpy(length, S->plen, P * sizeof(int32_t), hipMemcpyDeviceToHost));
-    if (status) TSL_HIP(hipMemcpy(status, S->pstatus, P, hipMemcpyDeviceToHost));
-    if (cost) TSL_HIP(hipMemcpy(cost, S->pcost, P * sizeof(uint32_t), hipMemcpyDeviceToHost));
-    return TSL_OK;
+    Stage st(&m->xbuf, &m->xbuf_bytes, q);
+    const int i_field = st.in(field, ncells * sizeof(uint32_t)), i_parent = st.in(parent, ncells), i_starts = st.in(starts, P * 3 * sizeof(int32_t)),
+              i_cells = st.out(cells, P * L * T::NCOMP * sizeof(int16_t)), i_len = st.out(length, P * sizeof(int32_t)), i_status = st.out(status, P),
+              i_cost = st.out(cost, P * sizeof(uint32_t));
+    if ((rc = st.upload())) return rc;
+    if ((rc = nf_paths_launch<T>(m, q, C, st.ptr<const uint32_t>(i_field), st.ptr<const uint8_t>(i_parent), st.ptr<const int32_t>(i_starts), n_starts, max_len,
+                                 st.ptr<int16_t>(i_cells), st.ptr<int32_t>(i_len), st.ptr<uint8_t>(i_status), st.ptr<uint32_t>(i_cost)))) return rc;
+    return st.download();
 }
 
 template <class T>

@@ -17,7 +17,8 @@
 //   cost: cost_unknown for an UNKNOWN cell, else lut[d2].
 //
 //   k_nav_project  one workgroup per brick column (bx, by), one lane per voxel column.  A lane's 16 layers of a brick are 64 contiguous bytes of tw and
-//                  16 of obs: five 16-byte loads give a 16-bit occupied and a 16-bit free mask; every band that meets the brick takes its layers out
+//                  16 of obs: five 16-byte loads give a 16-bit occupied and a 16-bit free mask (nav_column_load, tsl_nav_common.hpp, which
+//                  k_terrain_columns calls too: the one copy of the classes and of the NaN rule); every band that meets the brick takes its layers out
 //                  of them with an AND, two popcounts and a find-first / find-last.  The map is read once however many bands there are; an absent
 //                  brick and a brick no band meets cost no memory access.
 //   k_nav_rows     along j: g = the distance to the nearest obstacle of the row, capped at R + 1.  A wave per row: the row's obstacles become a bit
@@ -29,24 +30,19 @@
 //                  quarter of the LDS but left a 256^2 grid with 16 workgroups whose lanes each walk a chain of 16 + 2 R steps: at R = 254 the
 //                  pass took 101 us, latency of that one chain, on a device that was otherwise empty -- profiles/nav_grid.txt.)
 // The wall (flags bit 1) is the initial value of both passes.  No atomics, no iteration, no workgroup waits for another.
-#include "tsl_tsdf.hpp"
-#include <cmath>
+#include "tsl_nav_common.hpp"
+#include "tsl_stage.hpp"
 
 namespace tsl {
 
-#define NAV_MAX_BANDS 16
 #define NAV_TILE 64            // k_nav_cols: columns of a workgroup's tile, one per lane
 #define NAV_RB 4               // ... rows per lane
 #define NAV_ROWS (4 * NAV_RB)  // ... rows of the tile (four waves)
 #define NAV_G_FAR 255          // staged g of a row outside the grid: 255^2 > R * R + 1 for every R <= 254
 
-struct NavCfg {
-    int s, B, R, flags, min_occ, min_free, max_unknown, cost_unknown;
-    int uk0[NAV_MAX_BANDS], uk1[NAV_MAX_BANDS];      // the bands as unsigned layer indices k + Nz / 2
-    float thres;
-};
+struct NavCfg : NavBands { int R, flags, min_occ, min_free, max_unknown, cost_unknown; };
 
-struct NavState { void *cls, *g, *out, *lut; size_t b_cls, b_g, b_out, b_lut; };
+struct NavState { void *cls, *g; size_t b_cls, b_g; };      // scratch of the distance passes: the classes when the caller wants none, g
 
 // ---- projection -------------------------------------------------------------------------------------------------------------------------
 __global__ void __launch_bounds__(256) k_nav_project(MapDev M, NavCfg C, uint8_t* __restrict__ cls, uint16_t* __restrict__ counts, int16_t* __restrict__ span)
@@ -67,21 +63,8 @@ __global__ void __launch_bounds__(256) k_nav_project(MapDev M, NavCfg C, uint8_t
         if (!met) continue;
         const int P = T[bz];
         if (P < 0) continue;                                       // absent: 16 unknown layers, which the counts below get as the remainder
-        const uint4* __restrict__ tw4 = reinterpret_cast<const uint4*>(M.tw + (size_t)P * TSL_BRK3 + (size_t)tid * 16);
-        const uint4 ob = *reinterpret_cast<const uint4*>(M.obs + (size_t)P * TSL_BRK3 + (size_t)tid * 16);
-        const uint4 t0 = tw4[0], t1 = tw4[1], t2 = tw4[2], t3 = tw4[3];
-        const uint32_t tw[16] = { t0.x, t0.y, t0.z, t0.w, t1.x, t1.y, t1.z, t1.w, t2.x, t2.y, t2.z, t2.w, t3.x, t3.y, t3.z, t3.w };
-        const uint32_t ow[4] = { ob.x, ob.y, ob.z, ob.w };
-        uint32_t mo = 0, mf = 0;
-#pragma unroll
-        for (int lk = 0; lk < 16; ++lk) {
-            const bool seen = (int8_t)((ow[lk >> 2] >> ((lk & 3) * 8)) & 0xffu) > 0;
-            const float t = h2f((h16)(tw[lk] & 0xffffu));
-            const bool occ = seen && t < C.thres;                  // the test of q_occupied; false for a NaN
-            const bool fre = seen && !occ && t == t;               // a NaN is neither: it stays unknown
-            mo |= occ ? (1u << lk) : 0u;
-            mf |= fre ? (1u << lk) : 0u;
-        }
+        uint32_t mo, mf, tw[16];
+        nav_column_load(M, P, tid, C.thres, mo, mf, tw);
 #pragma unroll
         for (int b = 0; b < NAV_MAX_BANDS; ++b) {
             const int l0 = max(C.uk0[b], z0) - z0, l1 = min(C.uk1[b], z0 + 15) - z0;      // (a band beyond n_bands is empty: uk0 = 0, uk1 = -1)
@@ -209,7 +192,7 @@ void nav_release(tsl_tsdf* m)
 {
     NavState* S = m->nav;
     if (!S) return;
-    void* ptrs[] = { S->cls, S->g, S->out, S->lut };
+    void* ptrs[] = { S->cls, S->g };
     for (void* p : ptrs) if (p) (void)hipFree(p);
     delete S;
     m->nav = nullptr;
@@ -219,29 +202,16 @@ static int nav_check(tsl_tsdf* m, const tsl_nav_cfg* c, const void* lut, const v
                      NavCfg* C, const char* who)
 {
     const std::string w(who);
-    TSL_REQUIRE(m, w + ": null handle");
-    TSL_REQUIRE(c, w + ": null cfg");
-    TSL_REQUIRE(cls || d2 || cost || counts || span, w + ": every output is null");
-    TSL_REQUIRE(c->n_bands >= 1 && c->n_bands <= NAV_MAX_BANDS, w + ": n_bands must be 1 .. 16");
-    for (int b = 0; b < c->n_bands; ++b)
-        TSL_REQUIRE(c->k_min[b] <= c->k_max[b] && c->k_min[b] >= -(m->Nz / 2) && c->k_max[b] <= m->Nz / 2 - 1,
-                    w + ": band " + std::to_string(b) + " is empty (k_min > k_max) or leaves the volume");
-    TSL_REQUIRE(std::isfinite(c->free_thres), w + ": free_thres is not finite");
-    TSL_REQUIRE(c->min_occ >= 0, w + ": min_occ is negative");
-    TSL_REQUIRE(c->min_free >= 0, w + ": min_free is negative");
-    TSL_REQUIRE(c->radius >= 0 && c->radius <= 254, w + ": radius must be 0 .. 254 voxels");
-    TSL_REQUIRE((c->flags & ~3) == 0, w + ": unknown flags (bits 0 and 1 are defined)");
-    TSL_REQUIRE((cost != nullptr) == (lut != nullptr), w + ": cost and lut come together or not at all");
-    TSL_REQUIRE((long long)m->N * m->N * c->n_bands < (1ll << 31), w + ": the grids are too large (N * N * n_bands >= 2^31)");
-    C->s = m->cfg.is_global_map ? 0 : m->active;
-    C->B = c->n_bands; C->R = c->radius; C->flags = c->flags;
+    const int rc = nav_bands_check(m, c, lut, cls || d2 || cost || counts || span, cost, w, [&]() -> int {
+        TSL_REQUIRE(c->min_occ >= 0, w + ": min_occ is negative");
+        TSL_REQUIRE(c->min_free >= 0, w + ": min_free is negative");
+        return TSL_OK;
+    }, []() -> int { return TSL_OK; }, C);
+    if (rc) return rc;
+    C->R = c->radius; C->flags = c->flags;
     C->min_occ = c->min_occ; C->min_free = c->min_free; C->max_unknown = c->max_unknown; C->cost_unknown = c->cost_unknown;
-    for (int b = 0; b < NAV_MAX_BANDS; ++b) { C->uk0[b] = b < c->n_bands ? c->k_min[b] + m->Nz / 2 : 0; C->uk1[b] = b < c->n_bands ? c->k_max[b] + m->Nz / 2 : -1; }
-    C->thres = c->free_thres != 0.0f ? c->free_thres : m->surf_thres;
     return TSL_OK;
 }
-
-#define NAV_GROW(field, bytes_field, bytes) do { if ((rc = grow(&S->field, &S->bytes_field, (bytes)))) return rc; } while (0)
 
 // the two distance passes on q over a class plane [B][N][N] (g: B * N * N bytes of scratch); tsl_nav_terrain.hip runs them over its own classes
 int nav_edt_launch(tsl_tsdf* m, hipStream_t q, int N, int B, int R, int flags, int cost_unknown, const uint8_t* cls, uint8_t* g, const uint8_t* lut, uint16_t* d2,
@@ -269,8 +239,8 @@ static int nav_launch(tsl_tsdf* m, hipStream_t q, const NavCfg& C, const uint8_t
     const size_t cells = (size_t)N * N * C.B;
     const bool edt = d2 || cost;
     if (edt) {
-        NAV_GROW(g, b_g, cells);
-        if (!cls) { NAV_GROW(cls, b_cls, cells); cls = (uint8_t*)S->cls; }      // the distance pass reads the classes: they go to scratch
+        if ((rc = grow(&S->g, &S->b_g, cells))) return rc;
+        if (!cls) { if ((rc = grow(&S->cls, &S->b_cls, cells))) return rc; cls = (uint8_t*)S->cls; }      // the distance pass reads the classes: they go to scratch
     }
     if (cls || counts || span) {
         prof_begin(m, TSL_K_NAV_PROJECT, q);
@@ -294,26 +264,14 @@ int tsl_tsdf_nav_grid(tsl_tsdf* m, const tsl_nav_cfg* cfg, const uint8_t* lut, u
     int rc = nav_check(m, cfg, lut, cls, d2, cost, counts, span, &C, "nav_grid"); if (rc) return rc;
     TSL_HIP(hipSetDevice(m->device));
     const hipStream_t q = ms(m);                               // issues the queued frames: the pass runs behind them
-    if (!m->nav) m->nav = new NavState();
-    NavState* S = m->nav;
     const size_t cells = (size_t)m->N * m->N * C.B;
-    // one staging buffer: cls | cost | d2 | span | counts (every offset a multiple of 16)
-    const size_t c16 = (cells + 15) & ~(size_t)15;
-    const size_t o_cls = 0, o_cost = o_cls + (cls ? c16 : 0), o_d2 = o_cost + (cost ? c16 : 0), o_span = o_d2 + (d2 ? c16 * 2 : 0), o_cnt = o_span + (span ? c16 * 4 : 0),
-                 total = o_cnt + (counts ? c16 * 6 : 0);
-    NAV_GROW(out, b_out, total + 64);
-    const size_t lut_n = (size_t)C.R * C.R + 2;
-    if (lut) { NAV_GROW(lut, b_lut, lut_n); TSL_HIP(hipMemcpyAsync(S->lut, lut, lut_n, hipMemcpyHostToDevice, q)); }
-    char* base = (char*)S->out;
-    if ((rc = nav_launch(m, q, C, lut ? (const uint8_t*)S->lut : nullptr, cls ? (uint8_t*)(base + o_cls) : nullptr, d2 ? (uint16_t*)(base + o_d2) : nullptr,
-                         cost ? (uint8_t*)(base + o_cost) : nullptr, counts ? (uint16_t*)(base + o_cnt) : nullptr, span ? (int16_t*)(base + o_span) : nullptr))) return rc;
-    TSL_HIP(hipStreamSynchronize(q));
-    if (cls) TSL_HIP(hipMemcpy(cls, base + o_cls, cells, hipMemcpyDeviceToHost));
-    if (cost) TSL_HIP(hipMemcpy(cost, base + o_cost, cells, hipMemcpyDeviceToHost));
-    if (d2) TSL_HIP(hipMemcpy(d2, base + o_d2, cells * 2, hipMemcpyDeviceToHost));
-    if (span) TSL_HIP(hipMemcpy(span, base + o_span, cells * 4, hipMemcpyDeviceToHost));
-    if (counts) TSL_HIP(hipMemcpy(counts, base + o_cnt, cells * 6, hipMemcpyDeviceToHost));
-    return TSL_OK;
+    Stage st(&m->xbuf, &m->xbuf_bytes, q);
+    const int i_lut = st.in(lut, (size_t)C.R * C.R + 2), i_cls = st.out(cls, cells), i_cost = st.out(cost, cells), i_d2 = st.out(d2, cells * 2),
+              i_span = st.out(span, cells * 4), i_cnt = st.out(counts, cells * 6);
+    if ((rc = st.upload())) return rc;
+    if ((rc = nav_launch(m, q, C, st.ptr<const uint8_t>(i_lut), st.ptr<uint8_t>(i_cls), st.ptr<uint16_t>(i_d2), st.ptr<uint8_t>(i_cost), st.ptr<uint16_t>(i_cnt),
+                         st.ptr<int16_t>(i_span)))) return rc;
+    return st.download();
 }
 
 int tsl_tsdf_nav_grid_dev(tsl_tsdf* m, const tsl_nav_cfg* cfg, const void* lut_dev, void* cls_dev, void* d2_dev, void* cost_dev, void* counts_dev, void* span_dev,

@@ -29,7 +29,7 @@
 //     switches the slope test off.
 //   d2, cost: nav_grid's own passes (k_nav_rows, k_nav_cols) over this cls plane, with its radius, flags, lut and cost_unknown.
 //
-//   k_terrain_columns  one workgroup per brick column, one lane per voxel column, the loads and the masks of k_nav_project.  A lane walks its bricks from
+//   k_terrain_columns  one workgroup per brick column, one lane per voxel column, the loads and the masks of k_nav_project (nav_column_load).  A lane walks its bricks from
 //                      the top down, from the brick that holds layer min(max k_max + clearance, top), and carries two counters: the run of layers that
 //                      are not occupied and the run of FREE layers directly above.  They start at "unbounded" and 0 (above the volume nothing is occupied
 //                      and nothing is free; below the top the first brick's own layers settle them before a band's layer can ask).  An absent brick adds
@@ -40,25 +40,22 @@
 //   k_terrain_window   32 x 32 tiles of one band with a halo of max(window, slope_base) cells: at most 64 x 64 int16 heights in LDS, 32767 outside the
 //                      grid.  Maximum, minimum and count are separable: one pass along j into three [32 + 2 w][32] arrays, one along i out of them; then the
 //                      nine Sobel reads and the class.  No atomics, no iteration, no workgroup waits for another.
-#include "tsl_tsdf.hpp"
-#include <cmath>
+#include "tsl_nav_common.hpp"
+#include "tsl_stage.hpp"
 
 namespace tsl {
 
-#define TER_MAX_BANDS 16
 #define TER_TILE 32            // k_terrain_window: cells of a tile along each axis
 #define TER_DIM 64             // ... row stride of the staged heights: the tile and a halo of at most 16 cells on each side
 #define TER_NONE 32767         // height of a column without a support
 #define TER_UNBOUNDED (1 << 20)
 
-struct TerCfg {
-    int s, B, pick, clearance, free_run, window, slope_base, max_step, min_support, R, flags, cost_unknown;
+struct TerCfg : NavBands {
+    int pick, clearance, free_run, window, slope_base, max_step, min_support, R, flags, cost_unknown;
     uint32_t max_slope2;
-    int uk0[TER_MAX_BANDS], uk1[TER_MAX_BANDS];      // the bands as unsigned layer indices k + Nz / 2
-    float thres;
 };
 
-struct NavTerrainState { void *height, *col, *cls, *g, *out, *lut; size_t b_height, b_col, b_cls, b_g, b_out, b_lut; };
+struct NavTerrainState { void *height, *col, *cls, *g; size_t b_height, b_col, b_cls, b_g; };      // the planes a later stage reads when the caller wants none, g
 
 // ---- columns ------------------------------------------------------------------------------------------------------------------------------
 __global__ void __launch_bounds__(256) k_terrain_columns(MapDev M, TerCfg C, int16_t* __restrict__ height, uint8_t* __restrict__ col)
@@ -68,10 +65,10 @@ __global__ void __launch_bounds__(256) k_terrain_columns(MapDev M, TerCfg C, int
     const int tid = threadIdx.x;                                   // li * 16 + lj: the lane's 16 layers are voxels tid * 16 .. tid * 16 + 15 of a brick
     const int* __restrict__ T = M.table + (size_t)C.s * M.nb3 + (size_t)(bx * M.nbx + by) * M.nbz;
     uint32_t* st = s_ter_t + tid * 9;
-    int sup[TER_MAX_BANDS];                                        // the support as an unsigned layer, -1 = none so far
-    uint32_t pair[TER_MAX_BANDS];                                  // t_k | t_k1 << 16 of it
+    int sup[NAV_MAX_BANDS];                                        // the support as an unsigned layer, -1 = none so far
+    uint32_t pair[NAV_MAX_BANDS];                                  // t_k | t_k1 << 16 of it
 #pragma unroll
-    for (int b = 0; b < TER_MAX_BANDS; ++b) { sup[b] = -1; pair[b] = 0u; }
+    for (int b = 0; b < NAV_MAX_BANDS; ++b) { sup[b] = -1; pair[b] = 0u; }
     uint32_t anyocc = 0u, k1free = 0u;                             // bit b: band b holds an occupied voxel / the voxel above its support is FREE
     int umin = 0x7fffffff, umax = -1;                              // (uniform) the hull of the bands
     for (int b = 0; b < C.B; ++b) { umin = min(umin, C.uk0[b]); umax = max(umax, C.uk1[b]); }
@@ -83,21 +80,8 @@ __global__ void __launch_bounds__(256) k_terrain_columns(MapDev M, TerCfg C, int
         const int z0 = bz * 16;
         const int P = T[bz];
         if (P < 0) { nrun += 16; frun = 0; above_free = 0u; continue; }      // absent: 16 unknown layers
-        const uint4* __restrict__ tw4 = reinterpret_cast<const uint4*>(M.tw + (size_t)P * TSL_BRK3 + (size_t)tid * 16);
-        const uint4 ob = *reinterpret_cast<const uint4*>(M.obs + (size_t)P * TSL_BRK3 + (size_t)tid * 16);
-        const uint4 t0 = tw4[0], t1 = tw4[1], t2 = tw4[2], t3 = tw4[3];
-        const uint32_t tw[16] = { t0.x, t0.y, t0.z, t0.w, t1.x, t1.y, t1.z, t1.w, t2.x, t2.y, t2.z, t2.w, t3.x, t3.y, t3.z, t3.w };
-        const uint32_t ow[4] = { ob.x, ob.y, ob.z, ob.w };
-        uint32_t mo = 0u, mf = 0u;
-#pragma unroll
-        for (int lk = 0; lk < 16; ++lk) {
-            const bool seen = (int8_t)((ow[lk >> 2] >> ((lk & 3) * 8)) & 0xffu) > 0;
-            const float t = h2f((h16)(tw[lk] & 0xffffu));
-            const bool occ = seen && t < C.thres;                  // the classes of k_nav_project; false for a NaN
-            const bool fre = seen && !occ && t == t;               // a NaN is neither: it stays unknown
-            mo |= occ ? (1u << lk) : 0u;
-            mf |= fre ? (1u << lk) : 0u;
-        }
+        uint32_t mo, mf, tw[16];
+        nav_column_load(M, P, tid, C.thres, mo, mf, tw);
         uint32_t ms = 0u;                                          // the standable layers of the brick
 #pragma unroll
         for (int lk = 15; lk >= 0; --lk) {
@@ -114,7 +98,7 @@ __global__ void __launch_bounds__(256) k_terrain_columns(MapDev M, TerCfg C, int
             st[8] = tabove;
             const uint32_t mf17 = mf | (above_free << 16);
 #pragma unroll
-            for (int b = 0; b < TER_MAX_BANDS; ++b) {
+            for (int b = 0; b < NAV_MAX_BANDS; ++b) {
                 const int l0 = max(C.uk0[b], z0) - z0, l1 = min(C.uk1[b], z0 + 15) - z0;      // (a band beyond n_bands is empty: uk0 = 0, uk1 = -1)
                 if (l0 <= l1) {                                    // (uniform)
                     const uint32_t lm = ((2u << l1) - 1u) & ~((1u << l0) - 1u);
@@ -136,7 +120,7 @@ __global__ void __launch_bounds__(256) k_terrain_columns(MapDev M, TerCfg C, int
 
     const int ui = bx * 16 + (tid >> 4), uj = by * 16 + (tid & 15);
 #pragma unroll
-    for (int b = 0; b < TER_MAX_BANDS; ++b) {
+    for (int b = 0; b < NAV_MAX_BANDS; ++b) {
         if (b >= C.B) continue;                                    // (uniform)
         const size_t o = ((size_t)b * M.N + ui) * M.N + uj;
         int h = TER_NONE, c = ((anyocc >> b) & 1u) ? 1 : 2;
@@ -230,7 +214,7 @@ void nav_terrain_release(tsl_tsdf* m)
 {
     NavTerrainState* S = m->nav_terrain;
     if (!S) return;
-    void* ptrs[] = { S->height, S->col, S->cls, S->g, S->out, S->lut };
+    void* ptrs[] = { S->height, S->col, S->cls, S->g };
     for (void* p : ptrs) if (p) (void)hipFree(p);
     delete S;
     m->nav_terrain = nullptr;
@@ -239,32 +223,23 @@ void nav_terrain_release(tsl_tsdf* m)
 static int ter_check(tsl_tsdf* m, const tsl_nav_terrain_cfg* c, const void* lut, bool any_out, const void* cost, TerCfg* C, const char* who)
 {
     const std::string w(who);
-    TSL_REQUIRE(m, w + ": null handle");
-    TSL_REQUIRE(c, w + ": null cfg");
-    TSL_REQUIRE(any_out, w + ": every output is null");
-    TSL_REQUIRE(c->n_bands >= 1 && c->n_bands <= TER_MAX_BANDS, w + ": n_bands must be 1 .. 16");
-    for (int b = 0; b < c->n_bands; ++b)
-        TSL_REQUIRE(c->k_min[b] <= c->k_max[b] && c->k_min[b] >= -(m->Nz / 2) && c->k_max[b] <= m->Nz / 2 - 1,
-                    w + ": band " + std::to_string(b) + " is empty (k_min > k_max) or leaves the volume");
-    TSL_REQUIRE(std::isfinite(c->free_thres), w + ": free_thres is not finite");
-    TSL_REQUIRE(c->clearance >= 0 && c->clearance <= m->Nz, w + ": clearance must be 0 .. Nz layers");
-    TSL_REQUIRE(c->free_run >= 0 && c->free_run <= c->clearance, w + ": free_run must be 0 .. clearance");
-    TSL_REQUIRE(c->pick == 0 || c->pick == 1, w + ": pick must be 0 (lowest) or 1 (highest)");
-    TSL_REQUIRE(c->window >= 0 && c->window <= 16, w + ": window must be 0 .. 16 cells");
-    TSL_REQUIRE(c->slope_base >= 1 && c->slope_base <= 16, w + ": slope_base must be 1 .. 16 cells");
-    TSL_REQUIRE(c->max_step >= 0 && c->max_step <= 65534, w + ": max_step must be 0 .. 65534 sixteenths of a voxel");
-    TSL_REQUIRE(c->min_support >= 0, w + ": min_support is negative");
-    TSL_REQUIRE(c->radius >= 0 && c->radius <= 254, w + ": radius must be 0 .. 254 voxels");
-    TSL_REQUIRE((c->flags & ~3) == 0, w + ": unknown flags (bits 0 and 1 are defined)");
-    TSL_REQUIRE((cost != nullptr) == (lut != nullptr), w + ": cost and lut come together or not at all");
-    TSL_REQUIRE(m->Nz <= 4094, w + ": the volume is too high (Nz > 4094: height would not fit int16)");
-    TSL_REQUIRE((long long)m->N * m->N * c->n_bands < (1ll << 31), w + ": the grids are too large (N * N * n_bands >= 2^31)");
-    C->s = m->cfg.is_global_map ? 0 : m->active;
-    C->B = c->n_bands; C->pick = c->pick; C->clearance = c->clearance; C->free_run = c->free_run; C->window = c->window; C->slope_base = c->slope_base;
+    const int rc = nav_bands_check(m, c, lut, any_out, cost, w, [&]() -> int {
+        TSL_REQUIRE(c->clearance >= 0 && c->clearance <= m->Nz, w + ": clearance must be 0 .. Nz layers");
+        TSL_REQUIRE(c->free_run >= 0 && c->free_run <= c->clearance, w + ": free_run must be 0 .. clearance");
+        TSL_REQUIRE(c->pick == 0 || c->pick == 1, w + ": pick must be 0 (lowest) or 1 (highest)");
+        TSL_REQUIRE(c->window >= 0 && c->window <= 16, w + ": window must be 0 .. 16 cells");
+        TSL_REQUIRE(c->slope_base >= 1 && c->slope_base <= 16, w + ": slope_base must be 1 .. 16 cells");
+        TSL_REQUIRE(c->max_step >= 0 && c->max_step <= 65534, w + ": max_step must be 0 .. 65534 sixteenths of a voxel");
+        TSL_REQUIRE(c->min_support >= 0, w + ": min_support is negative");
+        return TSL_OK;
+    }, [&]() -> int {
+        TSL_REQUIRE(m->Nz <= 4094, w + ": the volume is too high (Nz > 4094: height would not fit int16)");
+        return TSL_OK;
+    }, C);
+    if (rc) return rc;
+    C->pick = c->pick; C->clearance = c->clearance; C->free_run = c->free_run; C->window = c->window; C->slope_base = c->slope_base;
     C->max_step = c->max_step; C->min_support = c->min_support; C->max_slope2 = c->max_slope2;
     C->R = c->radius; C->flags = c->flags; C->cost_unknown = c->cost_unknown;
-    for (int b = 0; b < TER_MAX_BANDS; ++b) { C->uk0[b] = b < c->n_bands ? c->k_min[b] + m->Nz / 2 : 0; C->uk1[b] = b < c->n_bands ? c->k_max[b] + m->Nz / 2 : -1; }
-    C->thres = c->free_thres != 0.0f ? c->free_thres : m->surf_thres;
     return TSL_OK;
 }
 
@@ -318,31 +293,14 @@ int tsl_tsdf_nav_terrain(tsl_tsdf* m, const tsl_nav_terrain_cfg* cfg, const uint
     int rc = ter_check(m, cfg, lut, height || col || step || nsup || slope2 || cls || d2 || cost, cost, &C, "nav_terrain"); if (rc) return rc;
     TSL_HIP(hipSetDevice(m->device));
     const hipStream_t q = ms(m);                               // issues the queued frames: the pass runs behind them
-    if (!m->nav_terrain) m->nav_terrain = new NavTerrainState();
-    NavTerrainState* S = m->nav_terrain;
     const size_t cells = (size_t)m->N * m->N * C.B;
-    // one staging buffer: slope2 | height | step | nsup | d2 | col | cls | cost (every offset a multiple of 16)
-    const size_t c16 = (cells + 15) & ~(size_t)15;
-    const size_t o_slope = 0, o_height = o_slope + (slope2 ? c16 * 4 : 0), o_step = o_height + (height ? c16 * 2 : 0), o_nsup = o_step + (step ? c16 * 2 : 0),
-                 o_d2 = o_nsup + (nsup ? c16 * 2 : 0), o_col = o_d2 + (d2 ? c16 * 2 : 0), o_cls = o_col + (col ? c16 : 0), o_cost = o_cls + (cls ? c16 : 0),
-                 total = o_cost + (cost ? c16 : 0);
-    TER_GROW(out, b_out, total + 64);
-    const size_t lut_n = (size_t)C.R * C.R + 2;
-    if (lut) { TER_GROW(lut, b_lut, lut_n); TSL_HIP(hipMemcpyAsync(S->lut, lut, lut_n, hipMemcpyHostToDevice, q)); }
-    char* base = (char*)S->out;
-    if ((rc = ter_launch(m, q, C, lut ? (const uint8_t*)S->lut : nullptr, height ? (int16_t*)(base + o_height) : nullptr, col ? (uint8_t*)(base + o_col) : nullptr,
-                         step ? (uint16_t*)(base + o_step) : nullptr, nsup ? (uint16_t*)(base + o_nsup) : nullptr, slope2 ? (uint32_t*)(base + o_slope) : nullptr,
-                         cls ? (uint8_t*)(base + o_cls) : nullptr, d2 ? (uint16_t*)(base + o_d2) : nullptr, cost ? (uint8_t*)(base + o_cost) : nullptr))) return rc;
-    TSL_HIP(hipStreamSynchronize(q));
-    if (slope2) TSL_HIP(hipMemcpy(slope2, base + o_slope, cells * 4, hipMemcpyDeviceToHost));
-    if (height) TSL_HIP(hipMemcpy(height, base + o_height, cells * 2, hipMemcpyDeviceToHost));
-    if (step) TSL_HIP(hipMemcpy(step, base + o_step, cells * 2, hipMemcpyDeviceToHost));
-    if (nsup) TSL_HIP(hipMemcpy(nsup, base + o_nsup, cells * 2, hipMemcpyDeviceToHost));
-    if (d2) TSL_HIP(hipMemcpy(d2, base + o_d2, cells * 2, hipMemcpyDeviceToHost));
-    if (col) TSL_HIP(hipMemcpy(col, base + o_col, cells, hipMemcpyDeviceToHost));
-    if (cls) TSL_HIP(hipMemcpy(cls, base + o_cls, cells, hipMemcpyDeviceToHost));
-    if (cost) TSL_HIP(hipMemcpy(cost, base + o_cost, cells, hipMemcpyDeviceToHost));
-    return TSL_OK;
+    Stage st(&m->xbuf, &m->xbuf_bytes, q);
+    const int i_lut = st.in(lut, (size_t)C.R * C.R + 2), i_slope = st.out(slope2, cells * 4), i_height = st.out(height, cells * 2), i_step = st.out(step, cells * 2),
+              i_nsup = st.out(nsup, cells * 2), i_d2 = st.out(d2, cells * 2), i_col = st.out(col, cells), i_cls = st.out(cls, cells), i_cost = st.out(cost, cells);
+    if ((rc = st.upload())) return rc;
+    if ((rc = ter_launch(m, q, C, st.ptr<const uint8_t>(i_lut), st.ptr<int16_t>(i_height), st.ptr<uint8_t>(i_col), st.ptr<uint16_t>(i_step), st.ptr<uint16_t>(i_nsup),
+                         st.ptr<uint32_t>(i_slope), st.ptr<uint8_t>(i_cls), st.ptr<uint16_t>(i_d2), st.ptr<uint8_t>(i_cost)))) return rc;
+    return st.download();
 }
 
 int tsl_tsdf_nav_terrain_dev(tsl_tsdf* m, const tsl_nav_terrain_cfg* cfg, const void* lut_dev, void* height_dev, void* col_dev, void* step_dev, void* nsup_dev,

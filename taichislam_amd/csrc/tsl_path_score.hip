@@ -9,6 +9,7 @@
 // stop flag the wave leaves behind the chunk that holds first_stop; the branch is wave-uniform (it depends on ballots only).  No LDS, no atomics, no
 // scratch, no barrier: the waves of a block never meet.  Read-only on the map.
 #include "tsl_esdf_sample.hpp"
+#include "tsl_stage.hpp"
 
 namespace tsl {
 
@@ -143,8 +144,6 @@ static int path_launch(tsl_tsdf* m, hipStream_t q, int mode, const PathDev& W, c
     return TSL_OK;
 }
 
-static size_t ps_align(size_t b) { return (b + 255) & ~(size_t)255; }
-
 }  // namespace tsl
 
 using namespace tsl;
@@ -161,21 +160,15 @@ int tsl_esdf_score_paths(tsl_tsdf* m, int mode, float unknown_value, const float
     if (!go) return TSL_OK;
     TSL_HIP(hipSetDevice(m->device));
     if ((rc = esdf_finish(m))) return rc;                      // the values handed out are the fixed point of the last update
-    const size_t c = (size_t)n, rows = c * (size_t)W.smax, wp_bytes = c * (size_t)K * 12;
-    const size_t o_len = ps_align(wp_bytes), o_out = o_len + ps_align(lengths ? c * 4 : 0), o_sd = o_out + ps_align(c * sizeof(tsl_path_score)),
-                 o_ss = o_sd + ps_align(sample_dist ? rows * 4 : 0), total = o_ss + (sample_status ? rows : 0);
-    if ((rc = grow(&m->xbuf, &m->xbuf_bytes, total + 64))) return rc;
-    char* base = (char*)m->xbuf;
-    TSL_HIP(hipMemcpy(base, waypoints, wp_bytes, hipMemcpyHostToDevice));
-    if (lengths) TSL_HIP(hipMemcpy(base + o_len, lengths, c * 4, hipMemcpyHostToDevice));
     const hipStream_t q = ms(m);
-    if ((rc = path_launch(m, q, mode, W, (const float*)base, lengths ? (const int*)(base + o_len) : nullptr, (int)n, (tsl_path_score*)(base + o_out),
-                          sample_dist ? (float*)(base + o_sd) : nullptr, sample_status ? (uint8_t*)(base + o_ss) : nullptr))) return rc;
-    TSL_HIP(hipStreamSynchronize(q));
-    TSL_HIP(hipMemcpy(out, base + o_out, c * sizeof(tsl_path_score), hipMemcpyDeviceToHost));
-    if (sample_dist) TSL_HIP(hipMemcpy(sample_dist, base + o_sd, rows * 4, hipMemcpyDeviceToHost));
-    if (sample_status) TSL_HIP(hipMemcpy(sample_status, base + o_ss, rows, hipMemcpyDeviceToHost));
-    return TSL_OK;
+    const size_t c = (size_t)n, rows = c * (size_t)W.smax;
+    Stage st(&m->xbuf, &m->xbuf_bytes, q);
+    const int i_wp = st.in(waypoints, c * (size_t)K * 12), i_len = st.in(lengths, c * 4), i_out = st.out(out, c * sizeof(tsl_path_score)),
+              i_sd = st.out(sample_dist, rows * 4), i_ss = st.out(sample_status, rows);
+    if ((rc = st.upload())) return rc;
+    if ((rc = path_launch(m, q, mode, W, st.ptr<const float>(i_wp), st.ptr<const int>(i_len), (int)n, st.ptr<tsl_path_score>(i_out), st.ptr<float>(i_sd),
+                          st.ptr<uint8_t>(i_ss)))) return rc;
+    return st.download();
 }
 
 int tsl_esdf_score_paths_dev(tsl_tsdf* m, int mode, float unknown_value, const void* waypoints_dev, const void* lengths_dev, int64_t n, int32_t K, int32_t sub,

@@ -3,6 +3,7 @@
 // DenseTSDF.is_occupy / is_unobserved (dense_tsdf.py:148-155), reference root; TopoGraphGen calls them 64-128 rays at a
 // time (topo_graph.py:444-507).  One thread per query, read-only gathers through the brick table.
 #include "tsl_query.hpp"
+#include "tsl_stage.hpp"
 #include <cfloat>
 
 namespace tsl {
@@ -92,15 +93,14 @@ int tsl_tsdf_query_points(tsl_tsdf* m, int mode, int param, const float* xyz, in
     TSL_REQUIRE(m && n >= 0 && (n == 0 || (xyz && out)), "query_points: bad argument"); TSL_REQUIRE(mode >= 0 && mode <= 2 && param >= 0 && param <= 16, "query_points: bad mode");
     if (n == 0) return TSL_OK;
     TSL_HIP(hipSetDevice(m->device));
-    int rc = grow(&m->xbuf, &m->xbuf_bytes, (size_t)n * 13 + 64); if (rc) return rc;
-    float* dx = (float*)m->xbuf; uint8_t* dout = (uint8_t*)m->xbuf + (size_t)n * 12;
-    TSL_HIP(hipMemcpy(dx, xyz, (size_t)n * 12, hipMemcpyHostToDevice));
-    hipLaunchKernelGGL(k_query_points, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ms(m), m->M, m->cfg.is_global_map ? 0 : m->active, m->P.vs, m->surf_thres, mode, param,
-                       (const float*)dx, (long long)n, dout);
+    const hipStream_t q = ms(m);
+    Stage st(&m->xbuf, &m->xbuf_bytes, q);
+    const int i_x = st.in(xyz, (size_t)n * 12), i_o = st.out(out, (size_t)n);
+    int rc = st.upload(); if (rc) return rc;
+    hipLaunchKernelGGL(k_query_points, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, q, m->M, m->cfg.is_global_map ? 0 : m->active, m->P.vs, m->surf_thres, mode, param,
+                       st.ptr<const float>(i_x), (long long)n, st.ptr<uint8_t>(i_o));
     TSL_HIP(hipGetLastError());
-    TSL_HIP(hipStreamSynchronize(ms(m)));
-    TSL_HIP(hipMemcpy(out, dout, (size_t)n, hipMemcpyDeviceToHost));
-    return TSL_OK;
+    return st.download();
 }
 
 int tsl_tsdf_query_raycast(tsl_tsdf* m, const float* pos, const float* dir, float max_dist, int64_t n, uint8_t* hit, float* end_xyz, float* len)
@@ -109,19 +109,16 @@ int tsl_tsdf_query_raycast(tsl_tsdf* m, const float* pos, const float* dir, floa
     TSL_REQUIRE(max_dist >= 0.0f && max_dist <= FLT_MAX, "query_raycast: max_dist is negative or not finite");      // (int)(inf / vs) steps would never end
     if (n == 0) return TSL_OK;
     TSL_HIP(hipSetDevice(m->device));
+    const hipStream_t q = ms(m);
     const size_t c = (size_t)n;
-    int rc = grow(&m->xbuf, &m->xbuf_bytes, c * 44 + 64); if (rc) return rc;
-    float* dpos = (float*)m->xbuf; float* ddir = dpos + c * 3; float* dend = ddir + c * 3; float* dlen = dend + c * 3; uint8_t* dhit = (uint8_t*)(dlen + c);
-    TSL_HIP(hipMemcpy(dpos, pos, c * 12, hipMemcpyHostToDevice));
-    TSL_HIP(hipMemcpy(ddir, dir, c * 12, hipMemcpyHostToDevice));
-    hipLaunchKernelGGL(k_query_raycast, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ms(m), m->M, m->cfg.is_global_map ? 0 : m->active, m->P.vs, (float)m->cfg.voxel_scale,
-                       m->surf_thres, max_dist, (const float*)dpos, (const float*)ddir, (long long)n, dhit, dend, dlen);
+    Stage st(&m->xbuf, &m->xbuf_bytes, q);
+    const int i_pos = st.in(pos, c * 12), i_dir = st.in(dir, c * 12), i_hit = st.out(hit, c), i_end = st.out(end_xyz, c * 12), i_len = st.out(len, c * 4);
+    int rc = st.upload(); if (rc) return rc;
+    hipLaunchKernelGGL(k_query_raycast, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, q, m->M, m->cfg.is_global_map ? 0 : m->active, m->P.vs, (float)m->cfg.voxel_scale,
+                       m->surf_thres, max_dist, st.ptr<const float>(i_pos), st.ptr<const float>(i_dir), (long long)n, st.ptr<uint8_t>(i_hit), st.ptr<float>(i_end),
+                       st.ptr<float>(i_len));
     TSL_HIP(hipGetLastError());
-    TSL_HIP(hipStreamSynchronize(ms(m)));
-    TSL_HIP(hipMemcpy(hit, dhit, c, hipMemcpyDeviceToHost));
-    TSL_HIP(hipMemcpy(end_xyz, dend, c * 12, hipMemcpyDeviceToHost));
-    TSL_HIP(hipMemcpy(len, dlen, c * 4, hipMemcpyDeviceToHost));
-    return TSL_OK;
+    return st.download();
 }
 
 int tsl_tsdf_query_points_dev(tsl_tsdf* m, int mode, int param, const void* xyz_dev, int64_t n, void* out_dev, void* user_stream)

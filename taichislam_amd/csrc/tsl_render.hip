@@ -24,6 +24,7 @@
 // jumps, never what it computes.
 #include <cmath>
 #include "tsl_interp.hpp"
+#include "tsl_stage.hpp"
 
 namespace tsl {
 
@@ -209,16 +210,12 @@ int tsl_tsdf_render_view(tsl_tsdf* m, const double R[9], const double T[3], cons
     int rc = render_check(m, R, T, v, depth, rgb, status, &W, "render_view"); if (rc) return rc;
     TSL_HIP(hipSetDevice(m->device));
     const hipStream_t q = ms(m);                               // issues the queued frames
-    const size_t c = (size_t)W.h * W.w, o_n = c * 4, o_c = o_n + (normal ? c * 12 : 0), o_s = o_c + (rgb ? c * 12 : 0);
-    if ((rc = grow(&m->xbuf, &m->xbuf_bytes, o_s + c + 64))) return rc;
-    char* base = (char*)m->xbuf;
-    if ((rc = render_launch(m, q, W, (float*)base, normal ? (float*)(base + o_n) : nullptr, rgb ? (float*)(base + o_c) : nullptr, (uint8_t*)(base + o_s)))) return rc;
-    TSL_HIP(hipStreamSynchronize(q));
-    TSL_HIP(hipMemcpy(depth, base, c * 4, hipMemcpyDeviceToHost));
-    if (normal) TSL_HIP(hipMemcpy(normal, base + o_n, c * 12, hipMemcpyDeviceToHost));
-    if (rgb) TSL_HIP(hipMemcpy(rgb, base + o_c, c * 12, hipMemcpyDeviceToHost));
-    TSL_HIP(hipMemcpy(status, base + o_s, c, hipMemcpyDeviceToHost));
-    return TSL_OK;
+    const size_t c = (size_t)W.h * W.w;
+    Stage st(&m->xbuf, &m->xbuf_bytes, q);
+    const int i_d = st.out(depth, c * 4), i_n = st.out(normal, c * 12), i_c = st.out(rgb, c * 12), i_s = st.out(status, c);
+    if ((rc = st.upload())) return rc;
+    if ((rc = render_launch(m, q, W, st.ptr<float>(i_d), st.ptr<float>(i_n), st.ptr<float>(i_c), st.ptr<uint8_t>(i_s)))) return rc;
+    return st.download();
 }
 
 int tsl_tsdf_render_view_dev(tsl_tsdf* m, const double R[9], const double T[3], const tsl_view_cfg* v, void* depth_dev, void* normal_dev, void* rgb_dev,

@@ -10,6 +10,7 @@
 //                    raises num_nodes after the loop, :442), so a launch never reads what it writes.
 // As in tsl_nav_corridor.hip: no atomic decides an output, every loop has a bound known at launch, every refusal comes before any launch.
 #include "tsl_query.hpp"
+#include "tsl_stage.hpp"
 #include <cfloat>
 #include <mutex>
 
@@ -270,20 +271,13 @@ static int rays_host(tsl_topo* t, const float* pos, const float* dir, const int3
     TSL_HIP(hipSetDevice(m->device));
     const hipStream_t q = ms(m);
     const size_t c = (size_t)n;
-    int rc = grow(&t->sbuf, &t->sbuf_bytes, c * 50 + 64); if (rc) return rc;
-    float* dpos = (float*)t->sbuf; float* ddir = dpos + c * 3; float* dend = ddir + c * 3; float* dlen = dend + c * 3; int* dpoly = (int*)(dlen + c); int* dskip = dpoly + c;
-    uint8_t* dhit = (uint8_t*)(dskip + c); uint8_t* dtype = dhit + c;
-    TSL_HIP(hipMemcpyAsync(dpos, pos, c * 12, hipMemcpyHostToDevice, q));
-    TSL_HIP(hipMemcpyAsync(ddir, dir, c * 12, hipMemcpyHostToDevice, q));
-    if (skip) TSL_HIP(hipMemcpyAsync(dskip, skip, c * 4, hipMemcpyHostToDevice, q));
-    if ((rc = rays_launch(t, q, dpos, ddir, skip ? dskip : nullptr, n, max_dist, backward, flags, dhit, dtype, dend, dlen, dpoly))) return rc;
-    TSL_HIP(hipStreamSynchronize(q));
-    if (hit) TSL_HIP(hipMemcpy(hit, dhit, c, hipMemcpyDeviceToHost));
-    if (type) TSL_HIP(hipMemcpy(type, dtype, c, hipMemcpyDeviceToHost));
-    if (end_xyz) TSL_HIP(hipMemcpy(end_xyz, dend, c * 12, hipMemcpyDeviceToHost));
-    if (len) TSL_HIP(hipMemcpy(len, dlen, c * 4, hipMemcpyDeviceToHost));
-    if (poly) TSL_HIP(hipMemcpy(poly, dpoly, c * 4, hipMemcpyDeviceToHost));
-    return TSL_OK;
+    Stage st(&t->sbuf, &t->sbuf_bytes, q);                                    // the kernel writes every plane: each keeps its room, a null one is not copied back
+    const int i_pos = st.in(pos, c * 12), i_dir = st.in(dir, c * 12), i_skip = st.in(skip, c * 4), i_hit = st.out(hit, c, true), i_type = st.out(type, c, true),
+              i_end = st.out(end_xyz, c * 12, true), i_len = st.out(len, c * 4, true), i_poly = st.out(poly, c * 4, true);
+    int rc = st.upload(); if (rc) return rc;
+    if ((rc = rays_launch(t, q, st.ptr<const float>(i_pos), st.ptr<const float>(i_dir), st.ptr<const int>(i_skip), n, max_dist, backward, flags, st.ptr<uint8_t>(i_hit),
+                          st.ptr<uint8_t>(i_type), st.ptr<float>(i_end), st.ptr<float>(i_len), st.ptr<int>(i_poly)))) return rc;
+    return st.download();
 }
 
 }  // namespace tsl
@@ -407,11 +401,11 @@ int tsl_topo_add_poly(tsl_topo* t, const float* tris, int32_t nf, const float* s
     const hipStream_t q = ms(m);
     if ((rc = topo_reserve(t, t->nf + nf, t->nn + 1))) return rc;
     const size_t c = (size_t)nf;
-    if ((rc = grow(&t->sbuf, &t->sbuf_bytes, c * 42 + 64))) return rc;
-    float* dtris = (float*)t->sbuf; int* dneigh = (int*)(dtris + c * 9); uint8_t* dfr = (uint8_t*)(dneigh + c); uint8_t* dwhy = dfr + c;
-    TSL_HIP(hipMemcpyAsync(dtris, tris, c * 36, hipMemcpyHostToDevice, q));
-    hipLaunchKernelGGL(k_topo_facelets, dim3((unsigned)((nf + 3) / 4)), dim3(256), 0, q, m->M, map_q(m), topo_dev(t), (const float*)dtris, nf, (int)t->nf, t->nn, start[0],
-                       start[1], start[2], max_dist, dfr, dwhy, dneigh);
+    Stage st(&t->sbuf, &t->sbuf_bytes, q);                                    // is_frontier and neigh are written whether asked for or not
+    const int i_tris = st.in(tris, c * 36), i_fr = st.out(is_frontier, c, true), i_why = st.out(reason, c), i_neigh = st.out(neigh, c * 4, true);
+    if ((rc = st.upload())) return rc;
+    hipLaunchKernelGGL(k_topo_facelets, dim3((unsigned)((nf + 3) / 4)), dim3(256), 0, q, m->M, map_q(m), topo_dev(t), st.ptr<const float>(i_tris), nf, (int)t->nf, t->nn,
+                       start[0], start[1], start[2], max_dist, st.ptr<uint8_t>(i_fr), st.ptr<uint8_t>(i_why), st.ptr<int>(i_neigh));
     TSL_HIP(hipGetLastError());
     // the node (add_mesh :384-405): the left-to-right f32 sum of (v0 + v1) + v2 over the facelets, divided by 3 * nf
     float node[3] = { 0.0f, 0.0f, 0.0f }, count = 0.0f;
@@ -423,10 +417,7 @@ int tsl_topo_add_poly(tsl_topo* t, const float* tris, int32_t nf, const float* s
     const int range[2] = { (int)t->nf, (int)t->nf + nf };
     TSL_HIP(hipMemcpyAsync(t->nctr + (size_t)t->nn * 3, node, 12, hipMemcpyHostToDevice, q));
     TSL_HIP(hipMemcpyAsync(t->nrange + (size_t)t->nn * 2, range, 8, hipMemcpyHostToDevice, q));
-    TSL_HIP(hipStreamSynchronize(q));
-    if (is_frontier) TSL_HIP(hipMemcpy(is_frontier, dfr, c, hipMemcpyDeviceToHost));
-    if (reason) TSL_HIP(hipMemcpy(reason, dwhy, c, hipMemcpyDeviceToHost));
-    if (neigh) TSL_HIP(hipMemcpy(neigh, dneigh, c * 4, hipMemcpyDeviceToHost));
+    if ((rc = st.download())) return rc;
     if (centre) for (int a = 0; a < 3; ++a) centre[a] = node[a];
     if (node_idx) *node_idx = t->nn;
     t->nf += nf; t->nn += 1;

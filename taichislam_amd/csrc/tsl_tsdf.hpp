@@ -226,14 +226,14 @@ struct GainState;                        // tsl_view_gain.hip: the pinned stagin
 void gain_release(tsl_tsdf* m);
 struct MeshIdxState;                     // tsl_mesh_indexed.hip: scratch and buffers of the indexed mesh (allocated by the first call)
 void mesh_indexed_release(tsl_tsdf* m);
-struct NavState;                         // tsl_nav_grid.hip: scratch and host staging of the navigation grids (allocated by the first call)
+struct NavState;                         // tsl_nav_grid.hip: scratch of the navigation grids (allocated by the first call)
 void nav_release(tsl_tsdf* m);
 struct NavFieldState;                    // tsl_nav_field_common.hpp: scratch, control block and pinned words of a cost-to-go solver (allocated by its first call)
 void nav_field_release(tsl_tsdf* m);     // tsl_nav_field.hip: the 2-D solver's instance
-struct NavTerrainState;                  // tsl_nav_terrain.hip: scratch and host staging of the terrain layers (allocated by the first call)
+struct NavTerrainState;                  // tsl_nav_terrain.hip: scratch of the terrain layers (allocated by the first call)
 void nav_terrain_release(tsl_tsdf* m);
 void nav_field3_release(tsl_tsdf* m);    // tsl_nav_field3.hip: the 3-D solver's instance
-struct NavCorridorState;                 // tsl_nav_corridor.hip: the bit volume, the per-cell boxes and the host staging of the corridors (allocated by the first call)
+struct NavCorridorState;                 // tsl_nav_corridor.hip: the bit volume and the per-cell boxes of the corridors (allocated by the first call)
 void nav_corridor_release(tsl_tsdf* m);
 void topo_map_gone(tsl_tsdf* m);         // tsl_topo.hip: the topology graphs bound to this map refuse every call from now on
 }  // namespace tsl
@@ -270,7 +270,7 @@ struct tsl_tsdf {
     float *exp_xyz, *exp_rgb, *exp_val; int* num_particles; int64_t max_disp;
     float* colormap;                     // [1024][3]
     float* pose_dev;                     // [npose][12] f32 (R row-major, T) for fusion
-    // sparse export staging
+    // the staging buffer of the sparse export and of every host-pointer form (tsl_stage.hpp says who shares it and why that is safe)
     void* xbuf; size_t xbuf_bytes;
     // mesh buffers (mesh_vertices / mesh_normals / mesh_colors, num_facelets)  marching_cube_mesher.py:16-22
     uint32_t* mesh_flags;                        // per pool brick: bit 0 a stored TSDF value < 0, bit 1 one that is not (k_mc_summary)

@@ -31,7 +31,7 @@
 //                        lanes of a tile drift apart (measured: slower than no skipping at all).
 // The estimate decides how far a ray jumps, never what it counts.
 #include <cmath>
-#include "tsl_tsdf.hpp"
+#include "tsl_stage.hpp"
 
 namespace tsl {
 
@@ -310,8 +310,6 @@ static int gain_launch(tsl_tsdf* m, hipStream_t q, const GainDev& W, const float
     return TSL_OK;
 }
 
-static size_t vg_align(size_t b) { return (b + 255) & ~(size_t)255; }
-
 }  // namespace tsl
 
 using namespace tsl;
@@ -326,21 +324,13 @@ int tsl_tsdf_view_gain(tsl_tsdf* m, const double* R, const double* T, int32_t n,
     TSL_HIP(hipSetDevice(m->device));
     const hipStream_t q = ms(m);                               // issues the queued frames
     const size_t rays = (size_t)n * W.h * W.w;
-    const size_t o_out = 0, o_ru = vg_align(sizeof(tsl_view_gain) * (size_t)n), o_rs = o_ru + (ray_unknown ? vg_align(rays * 4) : 0),
-                 total = o_rs + (ray_unknown ? rays : 0);
-    if ((rc = grow(&m->xbuf, &m->xbuf_bytes, total + 64))) return rc;
-    char* base = (char*)m->xbuf;
+    Stage st(&m->xbuf, &m->xbuf_bytes, q);
+    const int i_out = st.out(out, sizeof(tsl_view_gain) * (size_t)n), i_ru = st.out(ray_unknown, rays * 4), i_rs = st.out(ray_status, rays);
+    if ((rc = st.upload())) return rc;
     const float* poses;
     if ((rc = gain_stage(m, q, R, T, n, &poses))) return rc;
-    if ((rc = gain_launch(m, q, W, poses, n, (tsl_view_gain*)(base + o_out), ray_unknown ? (int*)(base + o_ru) : nullptr,
-                          ray_unknown ? (uint8_t*)(base + o_rs) : nullptr))) return rc;
-    TSL_HIP(hipStreamSynchronize(q));
-    TSL_HIP(hipMemcpy(out, base + o_out, sizeof(tsl_view_gain) * (size_t)n, hipMemcpyDeviceToHost));
-    if (ray_unknown) {
-        TSL_HIP(hipMemcpy(ray_unknown, base + o_ru, rays * 4, hipMemcpyDeviceToHost));
-        TSL_HIP(hipMemcpy(ray_status, base + o_rs, rays, hipMemcpyDeviceToHost));
-    }
-    return TSL_OK;
+    if ((rc = gain_launch(m, q, W, poses, n, st.ptr<tsl_view_gain>(i_out), st.ptr<int>(i_ru), st.ptr<uint8_t>(i_rs)))) return rc;
+    return st.download();
 }
 
 int tsl_tsdf_view_gain_dev(tsl_tsdf* m, const double* R, const double* T, int32_t n, const tsl_gain_cfg* cfg, void* out_dev, void* ray_unknown_dev,
