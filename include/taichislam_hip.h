@@ -355,6 +355,54 @@ int  tsl_esdf_score_paths(tsl_tsdf* m, int mode, float unknown_value, const floa
 int  tsl_esdf_score_paths_dev(tsl_tsdf* m, int mode, float unknown_value, const void* waypoints_dev, const void* lengths_dev, int64_t n, int32_t K,
                               int32_t sub, float radius, float margin, int32_t flags, void* out_dev, void* sample_dist_dev, void* sample_status_dev,
                               void* user_stream);
+/* batches of uniform cubic B-spline trajectories optimised against the ESDF in one launch (tsl_traj_opt.hip): the collision and smoothness costs of
+ * every trajectory with their gradients over the control points (linearize), and a momentum descent on them that runs all of its iterations inside the
+ * kernel (optimize).  Read-only on the map, one wave per trajectory.  Definition (tests/traj_opt_ref.py restates it in numpy bit
+ * for bit); every f32 product, sum and quotient below is rounded on its own, nothing is fused, divisions are correctly rounded:
+ *   Inputs.  ctrl f32 [n][K][3], control points in the frame of tsl_esdf_query_points; lengths int32 [n], nullable (NULL: every trajectory has K points),
+ *     each in 4 .. K -- the linearisation never reads the rows past a length; sub in 1 .. 64; clearance finite and >= 0; unknown_value as in
+ *     tsl_esdf_query_points.  n in 0 .. 2^20, K in 4 .. 256.
+ *   Samples.  A trajectory of length L has S = (L - 3) * sub + 1 samples j = 0 .. S-1: seg = min(j / sub, L - 4), m = j - seg * sub (the last sample has
+ *     m = sub).  u = (float)m / (float)sub, v = 1 - u, u2 = u * u, u3 = u2 * u; b0 = (v * v) * v, b1 = (3 u3 - 6 u2) + 4, b2 = ((3 u2 - 3 u3) + 3 u) + 1,
+ *     b3 = u3; w_i = b_i / 6.0f; per axis p = ((w0 c0 + w1 c1) + w2 c2) + w3 c3 with c_i = ctrl[seg + i].
+ *   Value of a sample: tsl_esdf_query_points mode 1 (trilinear, with its gradient g) at p.  A sample of status 0 counts as status 1 (unknown) when its
+ *     value or a component of g is not finite, or when it reads a voxel whose TSDF is NaN (as in tsl_esdf_score_paths).  A p that is not finite is
+ *     status 2.
+ *   q(t) = (int64)(int32)(fminf(fmaxf(t, -1024.0f), 1024.0f) * 1048576.0f), truncated toward zero: the 2^-20 fixed point of every gradient term.
+ *   Collision term, per sample of status 0: c = fminf(clearance - d, 1024.0f); the sample is PENALISED when c > 0, and then
+ *     cost_collision += (int64)((c * c) * 1048576.0f) (truncated) and, per axis a and i = 0 .. 3, Gp = -((2.0f * c) * g_a),
+ *     grad_collision[seg + i][a] += q(w_i * Gp).
+ *   Smoothness term, for i = 0 .. L - 3 and per axis: a = (c_i - (c_{i+1} + c_{i+1})) + c_{i+2}; a term whose a is not finite is skipped; otherwise with
+ *     ac = fminf(fmaxf(a, -1024.0f), 1024.0f): cost_smooth += (int64)((ac * ac) * 1048576.0f), grad_smooth[i] += q(2.0f * a),
+ *     grad_smooth[i + 1] += q(-4.0f * a), grad_smooth[i + 2] += q(2.0f * a).
+ *   tsl_traj_score (48 bytes, one per trajectory): n_samples = S; n_pen, the penalised samples; n_unknown and n_outside, the samples of status 1 and 2;
+ *     argmin / min_dist over the samples of status 0 by the (key(d), j) rule of tsl_path_score (-1 / +inf without one); short_update as there;
+ *     iters_done; cost_collision, cost_smooth.  All sums are integers: every field is independent of the schedule.
+ *   Descent (tsl_traj_opt; every f32 finite and >= 0, iters in 0 .. 1024, fix_head, fix_tail >= 0, flags bit 0 = stop at the first free
+ *     linearisation).  Velocities start at 0.  For k = 0 .. iters - 1: linearise the control points as they stand; with flags & 1 and n_pen == 0 stop,
+ *     iters_done = k; otherwise, for every control point i in fix_head .. L - 1 - fix_tail and every axis: gcf = (float)grad_collision *
+ *     9.5367431640625e-07f, gsf likewise (int64 -> f32 rounds to nearest even), g = w_collision * gcf + w_smooth * gsf,
+ *     v = momentum * v - step * g, a v that is not finite becomes 0, v = fminf(fmaxf(v, -max_move), max_move), c = c + v.  Without a stop
+ *     iters_done = iters.  The record (and the gradients of linearize) is the linearisation of the control points as they stand at the end, so iters = 0
+ *     is the pure linearisation and returns ctrl bit for bit; the rows past a length are copied through to ctrl_out.
+ *   history (nullable) int64 [n][iters + 1][2]: (cost_collision, cost_smooth) of linearisation k = 0 .. iters_done, -1 in the entries behind it.
+ *   grad_collision, grad_smooth (nullable, each on its own) int64 [n][K][3]; the rows past a length are 0.  out is nullable too.
+ * TSL_ERR_ARG, before anything is launched or written: whatever tsl_esdf_query_points refuses (no update since the map was created, reset or imported;
+ * the active submap changed); null ctrl (or ctrl_out, for optimize) with n > 0; n, K, sub, iters outside their ranges; a clearance, weight, step,
+ * momentum or max_move that is negative or not finite; fix_head or fix_tail negative, fix_head + fix_tail > K; flags with bits other than 1; and, in
+ * the host forms, a length outside 4 .. K -- the device forms CLAMP every length into 4 .. K.  n = 0 does nothing.
+ * The host forms stage through the handle's staging buffer and wait for the updates in flight first; the device forms are ASYNCHRONOUS and ordered like
+ * tsl_esdf_score_paths_dev.  out_dev, the gradient planes and history_dev must be aligned to 8 bytes, the rest to 4.  ctrl_out may not overlap ctrl. */
+typedef struct { int32_t n_samples, n_pen, n_unknown, n_outside, argmin; float min_dist; int32_t short_update, iters_done; int64_t cost_collision, cost_smooth; } tsl_traj_score;
+typedef struct { float clearance, w_collision, w_smooth, step, momentum, max_move; int32_t sub, iters, fix_head, fix_tail, flags, reserved_; } tsl_traj_opt;
+int  tsl_esdf_traj_linearize(tsl_tsdf* m, float unknown_value, const float* ctrl, const int32_t* lengths, int64_t n, int32_t K, int32_t sub, float clearance,
+                             tsl_traj_score* out, int64_t* grad_collision, int64_t* grad_smooth);
+int  tsl_esdf_traj_linearize_dev(tsl_tsdf* m, float unknown_value, const void* ctrl_dev, const void* lengths_dev, int64_t n, int32_t K, int32_t sub,
+                                 float clearance, void* out_dev, void* grad_collision_dev, void* grad_smooth_dev, void* user_stream);
+int  tsl_esdf_traj_optimize(tsl_tsdf* m, float unknown_value, const float* ctrl, const int32_t* lengths, int64_t n, int32_t K, const tsl_traj_opt* opt,
+                            float* ctrl_out, tsl_traj_score* out, int64_t* history);
+int  tsl_esdf_traj_optimize_dev(tsl_tsdf* m, float unknown_value, const void* ctrl_dev, const void* lengths_dev, int64_t n, int32_t K, const tsl_traj_opt* opt,
+                                void* ctrl_out_dev, void* out_dev, void* history_dev, void* user_stream);
 
 /* ---- view rendering (tsl_render.hip): what a camera at a pose would see of the TSDF -- depth, normal and colour per pixel.  It stands beside
  * BaseMap.raycast (mapping_common.py:165-178; tsl_tsdf_query_raycast above), which steps a whole voxel at a time and returns the last stepped

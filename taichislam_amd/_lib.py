@@ -160,6 +160,19 @@ class PathScore(C.Structure):
                 ("argmin", C.c_int32), ("min_dist", C.c_float), ("short_update", C.c_int32), ("cost", C.c_int64)]
 
 
+class TrajScore(C.Structure):
+    """tsl_traj_score: 48 bytes per trajectory, the layout of TRAJ_SCORE_DTYPE"""
+    _fields_ = [("n_samples", C.c_int32), ("n_pen", C.c_int32), ("n_unknown", C.c_int32), ("n_outside", C.c_int32), ("argmin", C.c_int32),
+                ("min_dist", C.c_float), ("short_update", C.c_int32), ("iters_done", C.c_int32), ("cost_collision", C.c_int64), ("cost_smooth", C.c_int64)]
+
+
+class TrajOpt(C.Structure):
+    """tsl_traj_opt (tsl_esdf_traj_optimize): flags bit 0 = stop at the first linearisation without a penalised sample"""
+    _fields_ = [("clearance", C.c_float), ("w_collision", C.c_float), ("w_smooth", C.c_float), ("step", C.c_float), ("momentum", C.c_float),
+                ("max_move", C.c_float), ("sub", C.c_int32), ("iters", C.c_int32), ("fix_head", C.c_int32), ("fix_tail", C.c_int32), ("flags", C.c_int32),
+                ("reserved_", C.c_int32)]
+
+
 class NavCfg(C.Structure):
     """tsl_nav_cfg (tsl_tsdf_nav_grid): n_bands bands of voxel layers k_min[b] .. k_max[b]; free_thres 0 = the map's surface threshold, min_occ / min_free
     0 = 1, max_unknown < 0 = no limit, radius in voxels, flags bit 0 = unknown cells are obstacles, bit 1 = so is the wall of the volume"""
@@ -307,6 +320,10 @@ SIGNATURES = {
     "tsl_esdf_query_points_dev": (C.c_int, [vp, C.c_int, f32, vp, i64, vp, vp, vp, vp]),
     "tsl_esdf_score_paths": (C.c_int, [vp, C.c_int, f32, vp, vp, i64, i32, i32, f32, f32, i32, vp, vp, vp]),
     "tsl_esdf_score_paths_dev": (C.c_int, [vp, C.c_int, f32, vp, vp, i64, i32, i32, f32, f32, i32, vp, vp, vp, vp]),
+    "tsl_esdf_traj_linearize": (C.c_int, [vp, f32, vp, vp, i64, i32, i32, f32, vp, vp, vp]),
+    "tsl_esdf_traj_linearize_dev": (C.c_int, [vp, f32, vp, vp, i64, i32, i32, f32, vp, vp, vp, vp]),
+    "tsl_esdf_traj_optimize": (C.c_int, [vp, f32, vp, vp, i64, i32, C.POINTER(TrajOpt), vp, vp, vp]),
+    "tsl_esdf_traj_optimize_dev": (C.c_int, [vp, f32, vp, vp, i64, i32, C.POINTER(TrajOpt), vp, vp, vp, vp]),
     "tsl_tsdf_render_view": (C.c_int, [vp, dp, dp, C.POINTER(ViewCfg), vp, vp, vp, vp]),
     "tsl_tsdf_render_view_dev": (C.c_int, [vp, dp, dp, C.POINTER(ViewCfg), vp, vp, vp, vp, vp]),
     "tsl_tsdf_align_linearize": (C.c_int, [vp, dp, dp, C.POINTER(AlignCfg), vp, C.POINTER(AlignSums)]),

@@ -1,6 +1,7 @@
-// tsl_esdf_sample.hpp -- the per-point ESDF sample shared by the point queries (tsl_esdf_query.hip) and the path scoring (tsl_path_score.hip): ONE copy of
-// the voxel / cell look-up, the value k_esdf_export reports and the interpolant with its gradient, so that both kernels return the same bits for a point
-// (tests/esdf_query_ref.py restates it in numpy; tests/path_score_ref.py builds on that).
+// tsl_esdf_sample.hpp -- the per-point ESDF sample shared by the point queries (tsl_esdf_query.hip), the path scoring (tsl_path_score.hip) and the
+// trajectory optimiser (tsl_traj_opt.hip): ONE copy of the voxel / cell look-up, the value k_esdf_export reports and the interpolant with its gradient,
+// so that all of them return the same bits for a point (tests/esdf_query_ref.py restates it in numpy; tests/path_score_ref.py and tests/traj_opt_ref.py
+// build on that).
 #pragma once
 #include "tsl_interp.hpp"      // lerp_f, cell_floor, the corner bricks and the interpolant: shared with tsl_render.hip
 

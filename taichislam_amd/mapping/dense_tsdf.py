@@ -230,6 +230,12 @@ PATH_SCORE_DTYPE = np.dtype({"names": ["n_samples", "first_stop", "n_hit", "n_un
                              "formats": [np.int32, np.int32, np.int32, np.int32, np.int32, np.int32, np.float32, np.int32, np.int64],
                              "offsets": [0, 4, 8, 12, 16, 20, 24, 28, 32], "itemsize": 40})
 
+# tsl_traj_score (include/taichislam_hip.h): 48 bytes per trajectory
+TRAJ_SCORE_DTYPE = np.dtype({"names": ["n_samples", "n_pen", "n_unknown", "n_outside", "argmin", "min_dist", "short_update", "iters_done", "cost_collision",
+                                       "cost_smooth"],
+                             "formats": [np.int32, np.int32, np.int32, np.int32, np.int32, np.float32, np.int32, np.int32, np.int64, np.int64],
+                             "offsets": [0, 4, 8, 12, 16, 20, 24, 28, 32, 40], "itemsize": 48})
+
 # tsl_view_gain (include/taichislam_hip.h): 64 bytes per pose at fixed offsets
 VIEW_GAIN_DTYPE = np.dtype({"names": ["n_unknown", "n_free", "vol_unknown", "vol_free", "n_hit", "n_range", "n_cut", "n_frontier"],
                             "formats": [np.int64, np.int64, np.int64, np.int64, np.int32, np.int32, np.int32, np.int32],
@@ -1867,6 +1873,120 @@ class DenseTSDF(BaseMap):
             out = {k: rec[k].copy() for k in PATH_SCORE_DTYPE.names}
         if samples:
             out["sample_dist"], out["sample_status"] = sd, ss
+        return out
+
+    def _traj_inputs(self, who, ctrl, lengths, refresh):
+        """(ctrl [n, K, 3] f32 contiguous, lengths int32 [n] or None, on the device?, one trajectory?) of traj_linearize / traj_optimize"""
+        if refresh:
+            if not getattr(self, "_esdf_ever", False):
+                raise _lib.TslError(f"{who}: call update_esdf first (refresh repeats the last update's parameters)")
+            self.update_esdf(gamma=self._esdf_gamma, max_dist=self._esdf_max_dist, wait=False)
+        dev = _is_device_tensor(ctrl)
+        if dev:
+            torch = _torch()
+            one = ctrl.dim() == 2
+            c = (ctrl[None] if one else ctrl).contiguous().float()
+        else:
+            c = np.asarray(ctrl, dtype=np.float32)
+            one = c.ndim == 2
+            c = np.ascontiguousarray(c[None] if one else c)
+        if c.ndim != 3 or c.shape[2] != 3:
+            raise ValueError(f"{who}: ctrl must be [n, K, 3] or [K, 3]")
+        n, K = int(c.shape[0]), int(c.shape[1])
+        ln = None
+        if lengths is not None and dev:
+            if not _is_device_tensor(lengths) or lengths.dtype != torch.int32:
+                raise TypeError(f"{who}: with torch ctrl, lengths must be a torch.int32 tensor on the same device")
+            ln = lengths.reshape(-1).contiguous()
+            if ln.shape[0] != n:
+                raise ValueError(f"{who}: one length per trajectory")
+        elif lengths is not None:
+            ln = np.asarray(lengths)
+            if not np.issubdtype(ln.dtype, np.integer):
+                raise TypeError(f"{who}: lengths must be integers")
+            if ln.shape != (n,):
+                raise ValueError(f"{who}: one length per trajectory")
+            if n and (ln.min() < 4 or ln.max() > K):
+                raise ValueError(f"{who}: a length outside 4 .. K")
+            ln = np.ascontiguousarray(ln, dtype=np.int32)
+        return c, ln, dev, one
+
+    @staticmethod
+    def _traj_record(rec, dev):
+        if not dev:
+            return {k: rec[k].copy() for k in TRAJ_SCORE_DTYPE.names}
+        torch = _torch()
+        out = {k: rec[:, i] for i, k in enumerate(TRAJ_SCORE_DTYPE.names[:8])}
+        out["min_dist"] = rec[:, 5].view(torch.float32)
+        out["cost_collision"] = rec[:, 8:10].contiguous().view(torch.int64).reshape(-1)
+        out["cost_smooth"] = rec[:, 10:12].contiguous().view(torch.int64).reshape(-1)
+        return out
+
+    def traj_linearize(self, ctrl, clearance, sub=4, lengths=None, gradients=True, unknown_value=float("nan"), refresh=True):
+        """The collision and smoothness costs of uniform cubic B-spline trajectories against the ESDF, with their gradients over the control points, in
+        one launch (tsl_traj_opt.hip).  ctrl f32 [n, K, 3] control points (a [K, 3] input is one trajectory), K in 4 .. 256, in
+        the frame of query_esdf; lengths (integers [n], 4 .. K, optional) gives the control points each trajectory uses.  Every span is sampled at `sub`
+        points (utils.nav.bspline_points gives the positions); a sample has query_esdf's trilinear value d and gradient, and is penalised by
+        (clearance - d)^2 where d < clearance.  Returns a dict of arrays per trajectory: n_samples, n_pen (penalised samples), n_unknown, n_outside
+        (samples the map does not know / outside the volume: counted, never penalised), argmin / min_dist (the closest known sample; -1 / +inf without
+        one), cost_collision and cost_smooth (int64, units of 2^-20 m^2), short_update, iters_done (0); with gradients=True also grad_collision and
+        grad_smooth, int64 [n, K, 3] in units of 2^-20 m.  Every field is exact and independent of the schedule.  numpy in -> numpy out; torch CUDA
+        tensors in (lengths then a torch.int32 tensor) -> torch tensors, asynchronously, ordered with torch.cuda.current_stream.  refresh as in
+        query_esdf."""
+        c, ln, dev, _ = self._traj_inputs("traj_linearize", ctrl, lengths, refresh)
+        n, K = int(c.shape[0]), int(c.shape[1])
+        if dev:
+            torch = _torch()
+            rec = torch.empty((n, 12), dtype=torch.int32, device=c.device)
+            gc = torch.empty((n, K, 3), dtype=torch.int64, device=c.device) if gradients else None
+            gs = torch.empty((n, K, 3), dtype=torch.int64, device=c.device) if gradients else None
+            ptr = lambda t: None if t is None else t.data_ptr()
+            _lib.check(self.L.tsl_esdf_traj_linearize_dev(self.h, float(unknown_value), c.data_ptr(), ptr(ln), n, K, int(sub), float(clearance), rec.data_ptr(),
+                                                          ptr(gc), ptr(gs), torch.cuda.current_stream(c.device).cuda_stream))
+        else:
+            rec = np.zeros(n, TRAJ_SCORE_DTYPE)
+            gc = np.zeros((n, K, 3), np.int64) if gradients else None
+            gs = np.zeros((n, K, 3), np.int64) if gradients else None
+            _lib.check(self.L.tsl_esdf_traj_linearize(self.h, float(unknown_value), _vp(c), _vp(ln), n, K, int(sub), float(clearance), _vp(rec), _vp(gc),
+                                                      _vp(gs)))
+        out = self._traj_record(rec, dev)
+        if gradients:
+            out["grad_collision"], out["grad_smooth"] = gc, gs
+        return out
+
+    def traj_optimize(self, ctrl, clearance, sub=4, iters=50, w_collision=1.0, w_smooth=1.0, step=0.05, momentum=0.8, max_move=None, fix_ends=3,
+                      stop_when_free=False, history=False, lengths=None, unknown_value=float("nan"), refresh=True):
+        """Pushes uniform cubic B-spline trajectories out of collision and smooths them: `iters` steps of a momentum descent on w_collision *
+        cost_collision + w_smooth * cost_smooth of traj_linearize, all inside one launch (tsl_traj_opt.hip).  Per step and
+        control point: v = momentum * v - step * gradient, clamped to +-max_move metres per axis (None: half a voxel), c += v.  The first and the last
+        fix_ends control points of every trajectory stay where they are (3 pins the end positions and tangents of a spline whose ends are tripled, as
+        utils.nav.bspline_from_path makes them).  stop_when_free ends a trajectory at its first linearisation without a penalised sample.  Returns
+        the dict of traj_linearize without the gradients, for the control points as they end (iters_done = the steps taken), and ctrl f32 [n, K, 3]
+        ([K, 3] for one trajectory); history=True adds history int64 [n, iters + 1, 2], (cost_collision, cost_smooth) of every linearisation and -1
+        behind a stop.  Samples that are unknown or outside pull nowhere: check n_unknown and n_outside, or re-check the result with
+        score_paths(bspline_points(ctrl, sub), clearance).  Arrays in and out as in traj_linearize."""
+        c, ln, dev, one = self._traj_inputs("traj_optimize", ctrl, lengths, refresh)
+        n, K = int(c.shape[0]), int(c.shape[1])
+        o = _lib.TrajOpt(clearance=float(clearance), w_collision=float(w_collision), w_smooth=float(w_smooth), step=float(step), momentum=float(momentum),
+                         max_move=0.5 * float(self.voxel_scale) if max_move is None else float(max_move), sub=int(sub), iters=int(iters),
+                         fix_head=int(fix_ends), fix_tail=int(fix_ends), flags=1 if stop_when_free else 0)
+        if dev:
+            torch = _torch()
+            rec = torch.empty((n, 12), dtype=torch.int32, device=c.device)
+            co = torch.empty_like(c)
+            hist = torch.empty((n, max(o.iters, 0) + 1, 2), dtype=torch.int64, device=c.device) if history else None
+            _lib.check(self.L.tsl_esdf_traj_optimize_dev(self.h, float(unknown_value), c.data_ptr(), None if ln is None else ln.data_ptr(), n, K, C.byref(o),
+                                                         co.data_ptr(), rec.data_ptr(), None if hist is None else hist.data_ptr(),
+                                                         torch.cuda.current_stream(c.device).cuda_stream))
+        else:
+            rec = np.zeros(n, TRAJ_SCORE_DTYPE)
+            co = np.zeros_like(c)
+            hist = np.zeros((n, max(o.iters, 0) + 1, 2), np.int64) if history else None
+            _lib.check(self.L.tsl_esdf_traj_optimize(self.h, float(unknown_value), _vp(c), _vp(ln), n, K, C.byref(o), _vp(co), _vp(rec), _vp(hist)))
+        out = self._traj_record(rec, dev)
+        out["ctrl"] = co[0] if one else co
+        if history:
+            out["history"] = hist
         return out
 
     def export_esdf_torch(self):

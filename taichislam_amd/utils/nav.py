@@ -179,3 +179,59 @@ def corridor_metres(boxes, volume=None, N=None, voxel=None):
         out[..., 2] = np.nan
     out[(b < 0).any(-1)] = np.nan
     return out
+
+
+# ---- B-spline trajectories: the samples of DenseTSDF.traj_linearize / traj_optimize, and a spline from a path --------------
+def bspline_basis(sub):
+    """f32 [sub + 1, 4]: the uniform cubic B-spline weights w_0 .. w_3 at u = m / sub, m = 0 .. sub, by the f32 recipe of the kernel (every product, sum
+    and quotient rounded on its own): rows 0 and sub are (1, 4, 1, 0) / 6 and (0, 1, 4, 1) / 6"""
+    f = np.float32
+    u = (np.arange(int(sub) + 1).astype(f) / f(sub)).astype(f)
+    v, u2 = f(1.0) - u, u * u
+    u3 = u2 * u
+    b = np.stack([(v * v) * v, (f(3.0) * u3 - f(6.0) * u2) + f(4.0), ((f(3.0) * u2 - f(3.0) * u3) + f(3.0) * u) + f(1.0), u3], 1)
+    return (b / f(6.0)).astype(f)
+
+
+def bspline_points(ctrl, sub, lengths=None):
+    """The sample positions of uniform cubic B-splines, bit for bit those DenseTSDF.traj_linearize evaluates: f32 [n, (K - 3) * sub + 1, 3] ([S, 3] for
+    one trajectory [K, 3]).  Sample j lies in span seg = min(j // sub, L - 4) at u = (j - seg * sub) / sub and is ((w0 c0 + w1 c1) + w2 c2) + w3 c3 over
+    the control points seg .. seg + 3.  With lengths (integers [n], 4 .. K) a trajectory has (L - 3) * sub + 1 samples and its row is padded with its
+    last sample, so that score_paths(bspline_points(ctrl, sub, lengths), clearance, lengths=(lengths - 3) * sub + 1) scores each on its own samples.
+    Host numpy; tensors are copied."""
+    c = _host(ctrl).astype(np.float32)
+    one = c.ndim == 2
+    c = c[None] if one else c
+    if c.ndim != 3 or c.shape[2] != 3 or c.shape[1] < 4:
+        raise ValueError("bspline_points: ctrl must be [n, K, 3] or [K, 3] with K >= 4")
+    n, K = c.shape[:2]
+    sub = int(sub)
+    if sub < 1:
+        raise ValueError("bspline_points: sub must be at least 1")
+    L = np.full(n, K, np.int64) if lengths is None else _host(lengths).astype(np.int64).reshape(n)
+    if n and (L.min() < 4 or L.max() > K):
+        raise ValueError("bspline_points: a length outside 4 .. K")
+    j = np.minimum(np.arange((K - 3) * sub + 1)[None, :], ((L - 3) * sub)[:, None])
+    seg = np.minimum(j // sub, (L - 4)[:, None])
+    w = bspline_basis(sub)[j - seg * sub]                           # [n, S, 4]
+    rows = np.arange(n)[:, None]
+    with np.errstate(invalid="ignore", over="ignore"):
+        p = ((w[..., 0:1] * c[rows, seg] + w[..., 1:2] * c[rows, seg + 1]) + w[..., 2:3] * c[rows, seg + 2]) + w[..., 3:4] * c[rows, seg + 3]
+    p = p.astype(np.float32)
+    return p[0] if one else p
+
+
+def bspline_from_path(points, K):
+    """K control points (float32 [K, 3], K >= 6) of a uniform cubic B-spline along a polyline: the polyline is resampled by arc length at K - 4 points,
+    its ends included, and both ends are tripled, so that the spline starts and ends AT the path's ends, at rest, and fix_ends = 3 of
+    DenseTSDF.traj_optimize pins them.  points: float [m, 3] metres in the frame of query_esdf, m >= 1 -- a path of DenseTSDF.nav_paths3d in metres, or
+    the centres of the boxes of corridor_metres.  Repeated points are fine.  Float64 host code."""
+    p = _host(points).astype(np.float64).reshape(-1, 3)
+    K = int(K)
+    if K < 6 or p.shape[0] < 1 or not np.isfinite(p).all():
+        raise ValueError("bspline_from_path: needs K >= 6 and at least one finite point")
+    s = np.concatenate([[0.0], np.cumsum(np.sqrt((np.diff(p, axis=0) ** 2).sum(1)))])
+    t = np.linspace(0.0, s[-1], K - 4)
+    mid = np.stack([np.interp(t, s, p[:, a]) for a in range(3)], 1)
+    mid[0], mid[-1] = p[0], p[-1]
+    return np.concatenate([mid[:1], mid[:1], mid, mid[-1:], mid[-1:]], 0).astype(np.float32)
