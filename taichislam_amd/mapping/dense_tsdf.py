@@ -11,34 +11,16 @@ import time
 import numpy as np
 
 from .. import _lib
+from ._sides import HOST, _is_device_tensor, _torch, _vp, device_dtypes, device_side, record_columns
 from .fields import DeviceArrayField, MapFieldRef, ScalarField
 from .mapping_common import BaseMap, _dptr, jet_colormap
 
 Wmax = 1000
 
 
-def _is_device_tensor(x):
-    return hasattr(x, "data_ptr") and hasattr(x, "is_cuda") and x.is_cuda
-
-
-def _vp(a):
-    return None if a is None else a.ctypes.data_as(C.c_void_p)
-
-
-_TORCH = None
-
-
-def _torch():
-    global _TORCH
-    if _TORCH is None:
-        import torch
-        _TORCH = torch
-    return _TORCH
-
-
 def _DEPTH_DTYPES(torch, _cache=[]):
     if not _cache:
-        _cache.append((torch.int16, getattr(torch, "uint16", torch.int16)))
+        _cache.append((torch.int16, device_dtypes(torch)["u2"]))
     return _cache[0]
 
 
@@ -118,6 +100,13 @@ def _point_cloud(xyz):
         return C.c_void_p(x.data_ptr()), int(x.shape[0]), x, True
     x = np.ascontiguousarray(np.asarray(xyz, dtype=np.float32).reshape(-1, 3))
     return _vp(x), int(x.shape[0]), x, False
+
+
+def _points_f32(xyz):
+    """(points f32 [n, 3] contiguous, their side) of the point queries: a numpy array, or a torch CUDA tensor that stays where it is"""
+    if _is_device_tensor(xyz):
+        return xyz.reshape(-1, 3).contiguous().float(), device_side(xyz.device)
+    return np.ascontiguousarray(np.asarray(xyz, dtype=np.float32).reshape(-1, 3)), HOST
 
 
 ALIGN_SCALE = 2.0 ** -20       # the sums of tsl_align_sums are 2^-20 fixed point
@@ -357,6 +346,54 @@ def _depth_image(depth):
     if d.ndim != 2:
         raise ValueError("depth must be a 2-d uint16 array")
     return _vp(d), d.shape, d, False
+
+
+def _polylines(who, arr, lengths, min_len, noun, name):
+    """(array f32 [n, K, 3] contiguous, lengths int32 [n] or None, side, was it one [K, 3] polyline?) of a batch of polylines -- the paths of score_paths, the
+    control points of traj_* -- a numpy array or a torch device tensor; `name` and `noun`: the argument and one of its rows, in messages.  The range of
+    the lengths, min_len .. K, is checked on the host side only: the device form reads no values (the library clamps them)."""
+    if _is_device_tensor(arr):
+        side, a = device_side(arr.device), arr
+    else:
+        side, a = HOST, np.asarray(arr, dtype=np.float32)
+    one = a.ndim == 2
+    if one:
+        a = a[None]
+    if a.ndim != 3 or a.shape[2] != 3:
+        raise ValueError(f"{who}: {name} must be [n, K, 3] or [K, 3]")
+    a = np.ascontiguousarray(a) if side is HOST else a.contiguous().float()
+    n, K = int(a.shape[0]), int(a.shape[1])
+    ln = lengths
+    if ln is not None and side is HOST:
+        ln = np.asarray(ln)
+        if not np.issubdtype(ln.dtype, np.integer):
+            raise TypeError(f"{who}: lengths must be integers")
+    elif ln is not None:
+        if not _is_device_tensor(ln) or ln.dtype != _torch().int32:
+            raise TypeError(f"{who}: with torch {name}, lengths must be a torch.int32 tensor on the same device")
+        ln = ln.reshape(-1).contiguous()
+    if ln is not None and tuple(ln.shape) != (n,):
+        raise ValueError(f"{who}: one length per {noun}")
+    if ln is not None and side is HOST:
+        if n and (ln.min() < min_len or ln.max() > K):
+            raise ValueError(f"{who}: a length outside {min_len} .. K")
+        ln = np.ascontiguousarray(ln, dtype=np.int32)
+    return a, ln, side, one
+
+
+def _index_rows(x, widths, message, clip=None):
+    """Rows of cell indices (goals, starts, cells: an array, a list or a tensor, which is read back) as int32 [S, w] with w among `widths`: the leading
+    `clip` columns (None = all) clipped to int32's range, so that the library sees a far index as outside, the rest keeping their low 32 bits.  An empty
+    input becomes [0, widths[-1]]; any other shape raises ValueError(message)."""
+    x = x.cpu().numpy() if hasattr(x, "is_cuda") else np.asarray(x)
+    if x.size == 0:
+        x = np.zeros((0, widths[-1]), np.int32)
+    if x.ndim != 2 or x.shape[1] not in widths:
+        raise ValueError(message)
+    x = x.astype(np.int64)
+    rows = np.ascontiguousarray((x & 0xffffffff).astype(np.uint32).view(np.int32))
+    rows[:, :clip] = np.clip(x[:, :clip], -(1 << 31), (1 << 31) - 1)
+    return rows
 
 
 class DenseTSDF(BaseMap):
@@ -818,19 +855,12 @@ class DenseTSDF(BaseMap):
 
     # ---- batched map queries (mapping_common.py:165-204; the reference exposes them as ti.funcs for TopoGraphGen) ----
     def _query_points(self, mode, xyz, param=0):
-        if _is_device_tensor(xyz):
-            # device tensors in, device tensor out, nothing waited for: the query runs on the map's stream behind every queued frame and
-            # torch's current stream is ordered after it (tsl_tsdf_query_points_dev)
-            torch = _torch()
-            x = xyz.reshape(-1, 3).contiguous().float()
-            out = torch.empty(x.shape[0], dtype=torch.uint8, device=x.device)
-            _lib.check(self.L.tsl_tsdf_query_points_dev(self.h, mode, int(param), x.data_ptr(), x.shape[0], out.data_ptr(),
-                                                        torch.cuda.current_stream(x.device).cuda_stream))
-            return out.bool()
-        xyz = np.ascontiguousarray(np.asarray(xyz, dtype=np.float32).reshape(-1, 3))
-        out = np.zeros(xyz.shape[0], np.uint8)
-        _lib.check(self.L.tsl_tsdf_query_points(self.h, mode, int(param), _vp(xyz), xyz.shape[0], _vp(out)))
-        return out.astype(bool)
+        # device tensors in, device tensor out, nothing waited for: the query runs on the map's stream behind every queued frame and
+        # torch's current stream is ordered after it (tsl_tsdf_query_points_dev)
+        x, side = _points_f32(xyz)
+        out = side.out(x.shape[0], "u1")
+        side.call(self.L.tsl_tsdf_query_points, self.L.tsl_tsdf_query_points_dev, self.h, mode, int(param), side.ptr(x), x.shape[0], side.ptr(out))
+        return out.astype(bool) if side is HOST else out.bool()
 
     def is_pos_occupy(self, xyz):
         return self._query_points(0, xyz)
@@ -844,23 +874,13 @@ class DenseTSDF(BaseMap):
     def raycast(self, pos, dir, max_dist):
         """Batched BaseMap.raycast: returns (hit bool[n], end xyz f32[n,3], length f32[n]); torch CUDA tensors in -> torch CUDA tensors
         out, asynchronously (the planner's 64-128 rays per node expansion, topo_graph.py:444-507, without a host round trip)."""
-        if _is_device_tensor(pos):
-            torch = _torch()
-            p = pos.reshape(-1, 3).contiguous().float(); d = dir.reshape(-1, 3).contiguous().float()
-            assert p.shape == d.shape and d.is_cuda
-            n = p.shape[0]
-            hit = torch.empty(n, dtype=torch.uint8, device=p.device); end = torch.empty((n, 3), dtype=torch.float32, device=p.device)
-            ln = torch.empty(n, dtype=torch.float32, device=p.device)
-            _lib.check(self.L.tsl_tsdf_query_raycast_dev(self.h, p.data_ptr(), d.data_ptr(), float(max_dist), n, hit.data_ptr(), end.data_ptr(),
-                                                         ln.data_ptr(), torch.cuda.current_stream(p.device).cuda_stream))
-            return hit.bool(), end, ln
-        pos = np.ascontiguousarray(np.asarray(pos, dtype=np.float32).reshape(-1, 3))
-        dir = np.ascontiguousarray(np.asarray(dir, dtype=np.float32).reshape(-1, 3))
-        assert pos.shape == dir.shape
-        n = pos.shape[0]
-        hit = np.zeros(n, np.uint8); end = np.zeros((n, 3), np.float32); ln = np.zeros(n, np.float32)
-        _lib.check(self.L.tsl_tsdf_query_raycast(self.h, _vp(pos), _vp(dir), float(max_dist), n, _vp(hit), _vp(end), _vp(ln)))
-        return hit.astype(bool), end, ln
+        (p, side), (d, side_d) = _points_f32(pos), _points_f32(dir)
+        assert p.shape == d.shape and (side is HOST) == (side_d is HOST)
+        n = p.shape[0]
+        hit, end, ln = side.out(n, "u1"), side.out((n, 3), "f4"), side.out(n, "f4")
+        side.call(self.L.tsl_tsdf_query_raycast, self.L.tsl_tsdf_query_raycast_dev, self.h, side.ptr(p), side.ptr(d), float(max_dist), n, side.ptr(hit),
+                  side.ptr(end), side.ptr(ln))
+        return (hit.astype(bool) if side is HOST else hit.bool()), end, ln
 
     # ---- view rendering (tsl_render.hip, DESIGN.md section 4.7; beside BaseMap.raycast, mapping_common.py:165-178) ----------
     def render_view(self, R, T, K=None, shape=(480, 640), t_min=None, t_max=None, step=None, normals=True, colors=None, device=False, skip=True):
@@ -878,21 +898,13 @@ class DenseTSDF(BaseMap):
         colors = bool(self.enable_texture) if colors is None else bool(colors)
         r, t = _dptr(R, 9)[1], _dptr(T, 3)[1]
         h, w = cfg.h, cfg.w
-        if device:
-            torch = _torch()
-            dev = torch.device(f"cuda:{self.device}")
-            depth = torch.empty((h, w), dtype=torch.float32, device=dev)
-            normal = torch.empty((h, w, 3), dtype=torch.float32, device=dev) if normals else None
-            rgb = torch.empty((h, w, 3), dtype=torch.float32, device=dev) if colors else None
-            status = torch.empty((h, w), dtype=torch.uint8, device=dev)
-            _lib.check(self.L.tsl_tsdf_render_view_dev(self.h, r, t, C.byref(cfg), depth.data_ptr(), None if normal is None else normal.data_ptr(),
-                                                       None if rgb is None else rgb.data_ptr(), status.data_ptr(), torch.cuda.current_stream(dev).cuda_stream))
-            return depth, normal, rgb, status
-        depth = np.empty((h, w), np.float32)
-        normal = np.empty((h, w, 3), np.float32) if normals else None
-        rgb = np.empty((h, w, 3), np.float32) if colors else None
-        status = np.empty((h, w), np.uint8)
-        _lib.check(self.L.tsl_tsdf_render_view(self.h, r, t, C.byref(cfg), _vp(depth), _vp(normal), _vp(rgb), _vp(status)))
+        side = device_side(self.device) if device else HOST
+        depth = side.out((h, w), "f4")
+        normal = side.out((h, w, 3), "f4") if normals else None
+        rgb = side.out((h, w, 3), "f4") if colors else None
+        status = side.out((h, w), "u1")
+        side.call(self.L.tsl_tsdf_render_view, self.L.tsl_tsdf_render_view_dev, self.h, r, t, C.byref(cfg), side.ptr(depth), side.ptr(normal), side.ptr(rgb),
+                  side.ptr(status))
         return depth, normal, rgb, status
 
     # ---- view gain (tsl_view_gain.hip) --------------------------------------------------------------
@@ -918,27 +930,20 @@ class DenseTSDF(BaseMap):
         Rn, Tn = gain_poses(R, T)
         n, h, w = Rn.shape[0], cfg.h, cfg.w
         r, t = Rn.ctypes.data_as(_lib.dp), Tn.ctypes.data_as(_lib.dp)
-        if device:
-            torch = _torch()
-            dev = torch.device(f"cuda:{self.device}")
-            rec = torch.zeros((n, 16), dtype=torch.int32, device=dev)
-            ru = torch.zeros((n, h, w), dtype=torch.int32, device=dev) if rays else None
-            rs = torch.zeros((n, h, w), dtype=torch.uint8, device=dev) if rays else None
-            if n:
-                _lib.check(self.L.tsl_tsdf_view_gain_dev(self.h, r, t, n, C.byref(cfg), rec.data_ptr(), None if ru is None else ru.data_ptr(),
-                                                         None if rs is None else rs.data_ptr(), torch.cuda.current_stream(dev).cuda_stream))
+        side = device_side(self.device) if device else HOST
+        rec = side.out((n, 16), "i4", zero=True)
+        ru = side.out((n, h, w), "i4", zero=True) if rays else None
+        rs = side.out((n, h, w), "u1", zero=True) if rays else None
+        if n or side is HOST:                                        # the device form of an empty batch is its zeroed tensors
+            side.call(self.L.tsl_tsdf_view_gain, self.L.tsl_tsdf_view_gain_dev, self.h, r, t, n, C.byref(cfg), side.ptr(rec), side.ptr(ru), side.ptr(rs))
+        if side is HOST:
+            rec = rec.view(VIEW_GAIN_DTYPE).reshape(n)
+            out = {k: rec[k].copy() for k in VIEW_GAIN_DTYPE.names}
+            dt = np.float32(cfg.dt) if cfg.dt != 0.0 else np.float32(0.75) * np.float32(self.voxel_scale)
+            out["unknown_volume"] = gain_volume(out["vol_unknown"], dt, cfg.K[0], cfg.K[4])
+            out["free_volume"] = gain_volume(out["vol_free"], dt, cfg.K[0], cfg.K[4])
+        else:
             out = {"records": rec}
-            if rays:
-                out["ray_unknown"], out["ray_status"] = ru, rs
-            return out
-        rec = np.zeros(n, VIEW_GAIN_DTYPE)
-        ru = np.zeros((n, h, w), np.int32) if rays else None
-        rs = np.zeros((n, h, w), np.uint8) if rays else None
-        _lib.check(self.L.tsl_tsdf_view_gain(self.h, r, t, n, C.byref(cfg), _vp(rec), _vp(ru), _vp(rs)))
-        out = {k: rec[k].copy() for k in VIEW_GAIN_DTYPE.names}
-        dt = np.float32(cfg.dt) if cfg.dt != 0.0 else np.float32(0.75) * np.float32(self.voxel_scale)
-        out["unknown_volume"] = gain_volume(out["vol_unknown"], dt, cfg.K[0], cfg.K[4])
-        out["free_volume"] = gain_volume(out["vol_free"], dt, cfg.K[0], cfg.K[4])
         if rays:
             out["ray_unknown"], out["ray_status"] = ru, rs
         return out
@@ -1032,6 +1037,25 @@ class DenseTSDF(BaseMap):
             raise ValueError("nav_grid: 1 .. 16 bands")
         return out
 
+    @staticmethod
+    def _nav_head(who, cfg, bl, free_thres, R, unknown_is_obstacle, wall_is_obstacle, cost_unknown, lut):
+        """Fills what NavCfg and NavTerrainCfg share -- the bands, free_thres, the radius in voxels, the flags, cost_unknown -- and returns the lut as the
+        u8 array of R * R + 2 costs the library reads, or None"""
+        if free_thres is not None and not float(free_thres) > 0.0:
+            raise ValueError(f"{who}: free_thres must be positive")
+        cfg.n_bands = len(bl)
+        for b, (k0, k1) in enumerate(bl):
+            cfg.k_min[b], cfg.k_max[b] = k0, k1
+        cfg.free_thres = 0.0 if free_thres is None else float(free_thres)
+        cfg.radius = R
+        cfg.flags = (1 if unknown_is_obstacle else 0) | (2 if wall_is_obstacle else 0)
+        cfg.cost_unknown = int(cost_unknown) & 0xff
+        if lut is not None:
+            lut = np.ascontiguousarray(np.asarray(lut, dtype=np.uint8).reshape(-1))
+            if lut.size != R * R + 2:
+                raise ValueError(f"{who}: lut must hold R * R + 2 = {R * R + 2} entries, not {lut.size}")
+        return lut
+
     def nav_grid(self, bands=None, z_range=None, radius=1.0, free_thres=None, min_occ=1, min_free=1, max_unknown=None, unknown_is_obstacle=False,
                  wall_is_obstacle=False, lut=None, cost_unknown=255, counts=False, span=False, device=False):
         """Height bands of the submap the point queries read (the active one; submap 0 on a global map) as 2-D navigation grids: what a 2-D planner or a
@@ -1052,44 +1076,20 @@ class DenseTSDF(BaseMap):
         if not math.isfinite(radius) or radius < 0.0:
             raise ValueError("nav_grid: radius must be finite and not negative")
         R = int(round(radius / float(self.voxel_scale)))
-        if free_thres is not None and not float(free_thres) > 0.0:
-            raise ValueError("nav_grid: free_thres must be positive")
         cfg = _lib.NavCfg()
-        cfg.n_bands = len(bl)
-        for b, (k0, k1) in enumerate(bl):
-            cfg.k_min[b], cfg.k_max[b] = k0, k1
-        cfg.free_thres = 0.0 if free_thres is None else float(free_thres)
+        lut = self._nav_head("nav_grid", cfg, bl, free_thres, R, unknown_is_obstacle, wall_is_obstacle, cost_unknown, lut)
         cfg.min_occ, cfg.min_free = int(min_occ), int(min_free)
         cfg.max_unknown = -1 if max_unknown is None else max(0, int(max_unknown))
-        cfg.radius = R
-        cfg.flags = (1 if unknown_is_obstacle else 0) | (2 if wall_is_obstacle else 0)
-        cfg.cost_unknown = int(cost_unknown) & 0xff
-        if lut is not None:
-            lut = np.ascontiguousarray(np.asarray(lut, dtype=np.uint8).reshape(-1))
-            if lut.size != R * R + 2:
-                raise ValueError(f"nav_grid: lut must hold R * R + 2 = {R * R + 2} entries, not {lut.size}")
         B, N = len(bl), self.N
         out = {"voxel": float(self.voxel_scale), "origin_xy": (-(N // 2) - 0.5) * float(self.voxel_scale), "bands": bl, "radius_vox": R}
-        if device:
-            torch = _torch()
-            dev = torch.device(f"cuda:{self.device}")
-            u16 = _DEPTH_DTYPES(torch)[1]
-            cls = torch.empty((B, N, N), dtype=torch.uint8, device=dev)
-            d2 = torch.empty((B, N, N), dtype=u16, device=dev)
-            cost = torch.empty((B, N, N), dtype=torch.uint8, device=dev) if lut is not None else None
-            cnt = torch.empty((B, N, N, 3), dtype=u16, device=dev) if counts else None
-            sp = torch.empty((B, N, N, 2), dtype=torch.int16, device=dev) if span else None
-            lut_d = torch.from_numpy(lut).to(dev) if lut is not None else None
-            ptr = lambda t: None if t is None else t.data_ptr()
-            _lib.check(self.L.tsl_tsdf_nav_grid_dev(self.h, C.byref(cfg), ptr(lut_d), ptr(cls), ptr(d2), ptr(cost), ptr(cnt), ptr(sp),
-                                                    torch.cuda.current_stream(dev).cuda_stream))
-        else:
-            cls = np.empty((B, N, N), np.uint8)
-            d2 = np.empty((B, N, N), np.uint16)
-            cost = np.empty((B, N, N), np.uint8) if lut is not None else None
-            cnt = np.empty((B, N, N, 3), np.uint16) if counts else None
-            sp = np.empty((B, N, N, 2), np.int16) if span else None
-            _lib.check(self.L.tsl_tsdf_nav_grid(self.h, C.byref(cfg), _vp(lut), _vp(cls), _vp(d2), _vp(cost), _vp(cnt), _vp(sp)))
+        side = device_side(self.device) if device else HOST
+        cls, d2 = side.out((B, N, N), "u1"), side.out((B, N, N), "u2")
+        cost = side.out((B, N, N), "u1") if lut is not None else None
+        cnt = side.out((B, N, N, 3), "u2") if counts else None
+        sp = side.out((B, N, N, 2), "i2") if span else None
+        lut = None if lut is None else side.put(lut)
+        side.call(self.L.tsl_tsdf_nav_grid, self.L.tsl_tsdf_nav_grid_dev, self.h, C.byref(cfg), side.ptr(lut), side.ptr(cls), side.ptr(d2), side.ptr(cost),
+                  side.ptr(cnt), side.ptr(sp))
         out["cls"], out["d2"] = cls, d2
         for k, v in (("cost", cost), ("counts", cnt), ("span", sp)):
             if v is not None:
@@ -1097,39 +1097,34 @@ class DenseTSDF(BaseMap):
         return out
 
     # ---- cost-to-go fields and paths: the one body of nav_field / nav_field3d and of nav_paths / nav_paths3d ----------------------
+    def _cost_u8(self, who, cost, device):
+        """A uint8 cost array, or the dict that holds one, on the host or on the device -> (contiguous array or tensor, its side): a tensor, or
+        device=True, gives the device side, on the map's device"""
+        if isinstance(cost, dict):
+            cost = cost["cost"]
+        on_dev = hasattr(cost, "is_cuda")
+        if not (on_dev or device):
+            cost = np.asarray(cost)
+            if cost.dtype != np.uint8:
+                raise ValueError(f"{who}: cost must be uint8")
+            return np.ascontiguousarray(cost), HOST
+        torch, side = _torch(), device_side(self.device)
+        ct = cost if on_dev else torch.from_numpy(np.ascontiguousarray(np.asarray(cost, dtype=np.uint8)))
+        if ct.dtype != torch.uint8:
+            raise ValueError(f"{who}: cost must be uint8")
+        return ct.to(side.dev).contiguous(), side
+
     def _nav_field_call(self, who, shape_rule, shape_text, cfg_cls, stats_cls, fn_host, fn_dev, cost, goals, neutral, lethal, connectivity, parent, max_rounds,
                         rounds_fixed, check_every, device):
         """who: the name in messages; shape_rule: the cost's shape -> the three extents, or None for one that is refused with shape_text; cfg_cls,
         stats_cls: the ctypes forms of the entry points fn_host (numpy) and fn_dev (torch)."""
-        if isinstance(cost, dict):
-            cost = cost["cost"]
-        on_dev = hasattr(cost, "is_cuda")
-        if on_dev or device:
-            torch = _torch()
-            dev = torch.device(f"cuda:{self.device}")
-            ct = cost if on_dev else torch.from_numpy(np.ascontiguousarray(np.asarray(cost, dtype=np.uint8)))
-            if ct.dtype != torch.uint8:
-                raise ValueError(f"{who}: cost must be uint8")
-            ct = ct.to(dev).contiguous()
-            shape = tuple(ct.shape)
-        else:
-            cost = np.asarray(cost)
-            if cost.dtype != np.uint8:
-                raise ValueError(f"{who}: cost must be uint8")
-            cost = np.ascontiguousarray(cost)
-            shape = tuple(cost.shape)
-        shape = shape_rule(shape)
+        cost, side = self._cost_u8(who, cost, device)
+        shape = shape_rule(tuple(cost.shape))
         if shape is None:
             raise ValueError(f"{who}: cost must be {shape_text}")
-        g = goals.cpu().numpy() if hasattr(goals, "is_cuda") else np.asarray(goals)
-        if g.size == 0:
-            g = np.zeros((0, 4), np.int32)
-        if g.ndim != 2 or g.shape[1] not in (3, 4):
-            raise ValueError(f"{who}: goals must be [S, 3] or [S, 4]")
-        g4 = np.zeros((g.shape[0], 4), np.int64)
-        g4[:, :g.shape[1]] = g
-        seeds = np.ascontiguousarray((g4 & 0xffffffff).astype(np.uint32).view(np.int32))
-        seeds[:, :3] = np.clip(g4[:, :3], -(1 << 31), (1 << 31) - 1).astype(np.int32)
+        g = _index_rows(goals, (3, 4), f"{who}: goals must be [S, 3] or [S, 4]", clip=3)
+        seeds = np.zeros((g.shape[0], 4), np.int32)                 # [S, 3]: the start value is 0
+        seeds[:, :g.shape[1]] = g
         cfg = cfg_cls(*shape)                                       # the three extents lead both structs
         cfg.neutral, cfg.lethal, cfg.connectivity = int(neutral), int(lethal), int(connectivity)
         cfg.max_rounds = 0 if max_rounds is None else int(max_rounds)
@@ -1139,20 +1134,16 @@ class DenseTSDF(BaseMap):
         cfg.check_every = 0 if check_every is None else int(check_every)
         S = seeds.shape[0]
         st = stats_cls()
-        if on_dev or device:
-            field = torch.empty(shape, dtype=getattr(torch, "uint32", torch.int32), device=dev)
-            par = torch.empty(shape, dtype=torch.uint8, device=dev) if parent else None
-            sd = torch.from_numpy(seeds).to(dev) if S else None
-            std = torch.zeros(6, dtype=torch.int32, device=dev)
-            ptr = lambda t: None if t is None else t.data_ptr()
-            _lib.check(fn_dev(self.h, C.byref(cfg), ptr(ct), ptr(sd), S, ptr(field), ptr(par), ptr(std), torch.cuda.current_stream(dev).cuda_stream))
+        field = side.out(shape, "u4")
+        par = side.out(shape, "u1") if parent else None
+        sd = side.put(seeds) if S else None
+        std = None if side is HOST else side.out(6, "i4", zero=True)         # the statistics: a struct on the host side, six words on the device
+        side.call(fn_host, fn_dev, self.h, C.byref(cfg), side.ptr(cost), side.ptr(sd), S, side.ptr(field), side.ptr(par),
+                  C.byref(st) if std is None else side.ptr(std))
+        if std is not None:
             sv = std.cpu().numpy()
             st.converged, st.rounds, st.n_bad_seeds = int(sv[0]), int(sv[1]), int(sv[4])
             st.tile_visits = int(sv[2:4].view(np.int64)[0])
-        else:
-            field = np.empty(shape, np.uint32)
-            par = np.empty(shape, np.uint8) if parent else None
-            _lib.check(fn_host(self.h, C.byref(cfg), _vp(cost), _vp(seeds) if S else None, S, _vp(field), _vp(par), C.byref(st)))
         out = {"field": field, "converged": int(st.converged), "rounds": int(st.rounds), "tile_visits": int(st.tile_visits), "n_bad_seeds": int(st.n_bad_seeds),
                "goals": seeds, "neutral": int(neutral), "lethal": int(lethal), "connectivity": int(connectivity)}
         if par is not None:
@@ -1165,12 +1156,7 @@ class DenseTSDF(BaseMap):
         if "parent" not in field_result:
             raise ValueError(f"{who}: the field was computed without parents ({field_who}(parent=True))")
         field, par = field_result["field"], field_result["parent"]
-        s = starts.cpu().numpy() if hasattr(starts, "is_cuda") else np.asarray(starts)
-        if s.size == 0:
-            s = np.zeros((0, 3), np.int32)
-        if s.ndim != 2 or s.shape[1] != 3:
-            raise ValueError(f"{who}: starts must be [P, 3]")
-        s = np.ascontiguousarray(np.clip(s.astype(np.int64), -(1 << 31), (1 << 31) - 1).astype(np.int32))
+        s = _index_rows(starts, (3,), f"{who}: starts must be [P, 3]")
         P, L = s.shape[0], int(max_len)
         if shape_text is not None and len(field.shape) != 3:
             raise ValueError(f"{who}: the field must be {shape_text}")
@@ -1178,20 +1164,13 @@ class DenseTSDF(BaseMap):
         cfg = cfg_cls(d0, d1, d2)
         Lc = max(L, 0)
         if hasattr(field, "is_cuda"):
-            torch = _torch()
-            dev = field.device
-            cells = torch.empty((P, Lc, width), dtype=torch.int16, device=dev)
-            length = torch.empty(P, dtype=torch.int32, device=dev)
-            status = torch.empty(P, dtype=torch.uint8, device=dev)
-            cost = torch.empty(P, dtype=getattr(torch, "uint32", torch.int32), device=dev)
-            sd = torch.from_numpy(s).to(dev) if P else None
-            _lib.check(fn_dev(self.h, C.byref(cfg), field.data_ptr(), par.data_ptr(), sd.data_ptr() if P else None, P, L, cells.data_ptr(), length.data_ptr(),
-                              status.data_ptr(), cost.data_ptr(), torch.cuda.current_stream(dev).cuda_stream))
+            side = device_side(field.device)
         else:
-            field, par = np.ascontiguousarray(field, dtype=np.uint32), np.ascontiguousarray(par, dtype=np.uint8)
-            cells = np.empty((P, Lc, width), np.int16)
-            length, status, cost = np.empty(P, np.int32), np.empty(P, np.uint8), np.empty(P, np.uint32)
-            _lib.check(fn_host(self.h, C.byref(cfg), _vp(field), _vp(par), _vp(s) if P else None, P, L, _vp(cells), _vp(length), _vp(status), _vp(cost)))
+            side, field, par = HOST, np.ascontiguousarray(field, dtype=np.uint32), np.ascontiguousarray(par, dtype=np.uint8)
+        cells, length, status, cost = side.out((P, Lc, width), "i2"), side.out(P, "i4"), side.out(P, "u1"), side.out(P, "u4")
+        sd = side.put(s) if P else None
+        side.call(fn_host, fn_dev, self.h, C.byref(cfg), side.ptr(field), side.ptr(par), side.ptr(sd), P, L, side.ptr(cells), side.ptr(length),
+                  side.ptr(status), side.ptr(cost))
         return {"cells": cells, "length": length, "status": status, "cost": cost}
 
     # ---- cost-to-go fields and paths (tsl_nav_field.hip) ------------------------------------------------
@@ -1248,23 +1227,9 @@ class DenseTSDF(BaseMap):
 
     # ---- safe corridors: free boxes around cells and along paths (tsl_nav_corridor.hip) -----------------
     def _nav_corridor_cost(self, who, cost, extent, free_below, device):
-        """the cost of nav_boxes / nav_corridor -> (array or tensor [D, H, W], on the device?, whether it had two axes, the filled NavCorridorCfg)"""
-        planes = False                                              # an int extent reaches along the leading axis only in a volume
-        if isinstance(cost, dict):
-            planes = "stride" not in cost                           # nav_grid / nav_terrain: planes; flight_volume: a volume
-            cost = cost["cost"]
-        on_dev = hasattr(cost, "is_cuda")
-        if on_dev or device:
-            torch = _torch()
-            ct = cost if on_dev else torch.from_numpy(np.ascontiguousarray(np.asarray(cost, dtype=np.uint8)))
-            if ct.dtype != torch.uint8:
-                raise ValueError(f"{who}: cost must be uint8")
-            cost = ct.to(torch.device(f"cuda:{self.device}")).contiguous()
-        else:
-            cost = np.asarray(cost)
-            if cost.dtype != np.uint8:
-                raise ValueError(f"{who}: cost must be uint8")
-            cost = np.ascontiguousarray(cost)
+        """the cost of nav_boxes / nav_corridor -> (array or tensor [D, H, W], its side, whether it had two axes, the filled NavCorridorCfg)"""
+        planes = isinstance(cost, dict) and "stride" not in cost    # an int extent reaches along the leading axis only in a volume (flight_volume's dict)
+        cost, side = self._cost_u8(who, cost, device)
         shape = tuple(cost.shape)
         if len(shape) not in (2, 3):
             raise ValueError(f"{who}: cost must be [H, W], [B, H, W] or [D, H, W]")
@@ -1282,7 +1247,7 @@ class DenseTSDF(BaseMap):
         cfg.free_below = int(free_below)
         cfg.ext_k, cfg.ext_i, cfg.ext_j = ext
         cfg.max_boxes = 1
-        return cost, (on_dev or bool(device)), two, cfg
+        return cost, side, two, cfg
 
     def nav_boxes(self, cost, cells, free_below=253, extent=16, device=False):
         """The free box around every cell of a list: an axis-aligned box of free cells that contains the cell, grown face by face in the fixed order -j, +j,
@@ -1296,40 +1261,27 @@ class DenseTSDF(BaseMap):
         cell outside (the box is six times -1).  numpy in gives numpy out; torch device tensors in (or device=True) give tensors out, asynchronously,
         ordered with torch.cuda.current_stream (tsl_tsdf_nav_boxes_dev); cells that are a device tensor are prepared on the device and not read by the
         host (the call still waits where the handle's scratch has to grow: the first call and any larger one)."""
-        cost, on_dev, two, cfg = self._nav_corridor_cost("nav_boxes", cost, extent, free_below, device or _is_device_tensor(cells))
+        cost, side, two, cfg = self._nav_corridor_cost("nav_boxes", cost, extent, free_below, device or _is_device_tensor(cells))
         width_ok = (2, 3) if two else (3,)
-        bad_cells = ValueError("nav_boxes: cells must be [S, 3]" + (" or [S, 2]" if two else ""))
+        bad_cells = "nav_boxes: cells must be [S, 3]" + (" or [S, 2]" if two else "")
         if _is_device_tensor(cells):
             # cells already on a device stay there: clipped, widened and made int32 by torch on the current stream, so the call does not wait
             torch = _torch()
             if cells.dim() != 2 or cells.shape[1] not in width_ok:
-                raise bad_cells
-            c = cells.to(cost.device).clamp(-(1 << 31), (1 << 31) - 1).to(torch.int32)
+                raise ValueError(bad_cells)
+            c = cells.to(side.dev).clamp(-(1 << 31), (1 << 31) - 1).to(torch.int32)
             if c.shape[1] == 2:
                 c = torch.cat([torch.zeros((c.shape[0], 1), dtype=torch.int32, device=c.device), c], 1)
             c = c.contiguous()
         else:
-            c = cells.numpy() if hasattr(cells, "is_cuda") else np.asarray(cells)
-            if c.size == 0:
-                c = np.zeros((0, 3), np.int32)
-            if c.ndim != 2 or c.shape[1] not in width_ok:
-                raise bad_cells
-            c = np.clip(c.astype(np.int64), -(1 << 31), (1 << 31) - 1).astype(np.int32)
+            c = _index_rows(cells, width_ok, bad_cells)
             if c.shape[1] == 2:
                 c = np.concatenate([np.zeros((c.shape[0], 1), np.int32), c], 1)
-            c = np.ascontiguousarray(c)
+            c = side.put(np.ascontiguousarray(c))
         S = c.shape[0]
-        if on_dev:
-            torch = _torch()
-            dev = cost.device
-            boxes = torch.empty((S, 6), dtype=torch.int16, device=dev)
-            flags = torch.empty(S, dtype=torch.uint8, device=dev)
-            cd = (c if hasattr(c, "is_cuda") else torch.from_numpy(c).to(dev)) if S else None
-            _lib.check(self.L.tsl_tsdf_nav_boxes_dev(self.h, C.byref(cfg), cost.data_ptr(), cd.data_ptr() if S else None, S, boxes.data_ptr(), flags.data_ptr(),
-                                                     torch.cuda.current_stream(dev).cuda_stream))
-        else:
-            boxes, flags = np.empty((S, 6), np.int16), np.empty(S, np.uint8)
-            _lib.check(self.L.tsl_tsdf_nav_boxes(self.h, C.byref(cfg), _vp(cost), _vp(c) if S else None, S, _vp(boxes), _vp(flags)))
+        boxes, flags = side.out((S, 6), "i2"), side.out(S, "u1")
+        side.call(self.L.tsl_tsdf_nav_boxes, self.L.tsl_tsdf_nav_boxes_dev, self.h, C.byref(cfg), side.ptr(cost), side.ptr(c) if S else None, S,
+                  side.ptr(boxes), side.ptr(flags))
         return {"boxes": boxes, "flags": flags}
 
     def nav_corridor(self, cost, paths, free_below=253, extent=16, max_boxes=64, planes=None):
@@ -1344,7 +1296,7 @@ class DenseTSDF(BaseMap):
         tensors out, asynchronously on torch.cuda.current_stream (tsl_tsdf_nav_corridor_dev); otherwise numpy arrays."""
         cells, length = (paths["cells"], paths["length"]) if isinstance(paths, dict) else paths
         want_dev = hasattr(cells, "is_cuda") or hasattr(cost, "is_cuda") or (isinstance(cost, dict) and hasattr(cost["cost"], "is_cuda"))
-        cost, on_dev, two, cfg = self._nav_corridor_cost("nav_corridor", cost, extent, free_below, want_dev)
+        cost, side, two, cfg = self._nav_corridor_cost("nav_corridor", cost, extent, free_below, want_dev)
         if len(cells.shape) != 3 or cells.shape[2] not in (2, 3):
             raise ValueError("nav_corridor: cells must be [P, L, 3] or [P, L, 2]")
         P, L, width = (int(v) for v in cells.shape)
@@ -1352,35 +1304,25 @@ class DenseTSDF(BaseMap):
             raise ValueError("nav_corridor: length must be [P]")
         Q = int(max_boxes)
         cfg.max_boxes = Q
-        if on_dev:
-            torch = _torch()
-            dev = cost.device
-            as_t = lambda a, dt: (a if hasattr(a, "is_cuda") else torch.from_numpy(np.ascontiguousarray(np.asarray(a)))).to(device=dev, dtype=dt)
-            cd, ld = as_t(cells, torch.int16), as_t(length, torch.int32).contiguous()
-            if width == 2:
-                pl = torch.zeros(P, dtype=torch.int16, device=dev) if planes is None else as_t(planes, torch.int16).reshape(P)
-                cd = torch.cat([pl[:, None, None].expand(P, L, 1), cd], 2)
-            cd = cd.contiguous()
-            Qc = max(Q, 0)
-            boxes = torch.empty((P, Qc, 6), dtype=torch.int16, device=dev)
-            seed = torch.empty((P, Qc), dtype=torch.int32, device=dev)
-            link = torch.empty((P, Qc), dtype=torch.uint8, device=dev)
-            count = torch.empty(P, dtype=torch.int32, device=dev)
-            status = torch.empty(P, dtype=torch.uint8, device=dev)
-            ptr = lambda t: t.data_ptr() if P else None
-            _lib.check(self.L.tsl_tsdf_nav_corridor_dev(self.h, C.byref(cfg), cost.data_ptr(), ptr(cd), ptr(ld), P, L, boxes.data_ptr(), seed.data_ptr(),
-                                                        link.data_ptr(), count.data_ptr(), status.data_ptr(), torch.cuda.current_stream(dev).cuda_stream))
-        else:
+        if side is HOST:
             cd, ld = np.asarray(cells, dtype=np.int16), np.ascontiguousarray(np.asarray(length, dtype=np.int32))
             if width == 2:
                 pl = np.zeros(P, np.int16) if planes is None else np.asarray(planes, dtype=np.int16).reshape(P)
                 cd = np.concatenate([np.broadcast_to(pl[:, None, None], (P, L, 1)), cd], 2)
             cd = np.ascontiguousarray(cd)
-            Qc = max(Q, 0)
-            boxes, seed, link = np.empty((P, Qc, 6), np.int16), np.empty((P, Qc), np.int32), np.empty((P, Qc), np.uint8)
-            count, status = np.empty(P, np.int32), np.empty(P, np.uint8)
-            _lib.check(self.L.tsl_tsdf_nav_corridor(self.h, C.byref(cfg), _vp(cost), _vp(cd) if P else None, _vp(ld) if P else None, P, L, _vp(boxes), _vp(seed),
-                                                    _vp(link), _vp(count), _vp(status)))
+        else:                                                       # paths that are tensors are prepared by torch: the host does not read them
+            torch = _torch()
+            as_t = lambda a, dt: (a if hasattr(a, "is_cuda") else torch.from_numpy(np.ascontiguousarray(np.asarray(a)))).to(device=side.dev, dtype=dt)
+            cd, ld = as_t(cells, torch.int16), as_t(length, torch.int32).contiguous()
+            if width == 2:
+                pl = torch.zeros(P, dtype=torch.int16, device=side.dev) if planes is None else as_t(planes, torch.int16).reshape(P)
+                cd = torch.cat([pl[:, None, None].expand(P, L, 1), cd], 2)
+            cd = cd.contiguous()
+        Qc = max(Q, 0)
+        boxes, seed, link = side.out((P, Qc, 6), "i2"), side.out((P, Qc), "i4"), side.out((P, Qc), "u1")
+        count, status = side.out(P, "i4"), side.out(P, "u1")
+        side.call(self.L.tsl_tsdf_nav_corridor, self.L.tsl_tsdf_nav_corridor_dev, self.h, C.byref(cfg), side.ptr(cost), side.ptr(cd) if P else None,
+                  side.ptr(ld) if P else None, P, L, side.ptr(boxes), side.ptr(seed), side.ptr(link), side.ptr(count), side.ptr(status))
         return {"boxes": boxes, "seed": seed, "link": link, "count": count, "status": status, "free_below": int(free_below),
                 "extent": (int(cfg.ext_k), int(cfg.ext_i), int(cfg.ext_j))}
 
@@ -1475,42 +1417,18 @@ class DenseTSDF(BaseMap):
             ms = min(65534, int(round(max_step / vs * 16.0)))
         from ..utils.nav import terrain_slope2
         ms2 = terrain_slope2(max_slope_deg, min(s, 16))
-        if free_thres is not None and not float(free_thres) > 0.0:
-            raise ValueError("nav_terrain: free_thres must be positive")
         cfg = _lib.NavTerrainCfg()
-        cfg.n_bands = len(bl)
-        for b, (k0, k1) in enumerate(bl):
-            cfg.k_min[b], cfg.k_max[b] = k0, k1
-        cfg.free_thres = 0.0 if free_thres is None else float(free_thres)
+        lut = self._nav_head("nav_terrain", cfg, bl, free_thres, R, unknown_is_obstacle, wall_is_obstacle, cost_unknown, lut)
         cfg.clearance, cfg.free_run, cfg.pick, cfg.window, cfg.slope_base = cl, int(free_run), 0 if pick == "lowest" else 1, w, s
         cfg.max_step, cfg.min_support, cfg.max_slope2 = ms, int(min_support), ms2
-        cfg.radius = R
-        cfg.flags = (1 if unknown_is_obstacle else 0) | (2 if wall_is_obstacle else 0)
-        cfg.cost_unknown = int(cost_unknown) & 0xff
-        if lut is not None:
-            lut = np.ascontiguousarray(np.asarray(lut, dtype=np.uint8).reshape(-1))
-            if lut.size != R * R + 2:
-                raise ValueError(f"nav_terrain: lut must hold R * R + 2 = {R * R + 2} entries, not {lut.size}")
         B, N = len(bl), self.N
         out = {"voxel": vs, "origin_xy": (-(N // 2) - 0.5) * vs, "bands": bl, "radius_vox": R, "height_unit": vs / 16.0, "clearance_vox": cl,
                "free_run": int(free_run), "pick": pick, "window_vox": w, "slope_base_vox": s, "max_step_units": ms, "max_slope2": ms2, "min_support": int(min_support)}
-        names = ("height", "col", "step", "nsup", "slope2", "cls", "d2") + (("cost",) if lut is not None else ())
-        if device:
-            torch = _torch()
-            dev = torch.device(f"cuda:{self.device}")
-            u16 = _DEPTH_DTYPES(torch)[1]
-            kinds = {"height": torch.int16, "col": torch.uint8, "step": u16, "nsup": u16, "slope2": getattr(torch, "uint32", torch.int32), "cls": torch.uint8,
-                     "d2": u16, "cost": torch.uint8}
-            pl = {k: torch.empty((B, N, N), dtype=kinds[k], device=dev) for k in names}
-            lut_d = torch.from_numpy(lut).to(dev) if lut is not None else None
-            p = lambda k: pl[k].data_ptr() if k in pl else None
-            _lib.check(self.L.tsl_tsdf_nav_terrain_dev(self.h, C.byref(cfg), None if lut_d is None else lut_d.data_ptr(), p("height"), p("col"), p("step"), p("nsup"),
-                                                       p("slope2"), p("cls"), p("d2"), p("cost"), torch.cuda.current_stream(dev).cuda_stream))
-        else:
-            kinds = {"height": np.int16, "col": np.uint8, "step": np.uint16, "nsup": np.uint16, "slope2": np.uint32, "cls": np.uint8, "d2": np.uint16, "cost": np.uint8}
-            pl = {k: np.empty((B, N, N), kinds[k]) for k in names}
-            p = lambda k: _vp(pl[k]) if k in pl else None
-            _lib.check(self.L.tsl_tsdf_nav_terrain(self.h, C.byref(cfg), _vp(lut), p("height"), p("col"), p("step"), p("nsup"), p("slope2"), p("cls"), p("d2"), p("cost")))
+        kinds = {"height": "i2", "col": "u1", "step": "u2", "nsup": "u2", "slope2": "u4", "cls": "u1", "d2": "u2", "cost": "u1"}
+        side = device_side(self.device) if device else HOST
+        pl = {k: side.out((B, N, N), kind) for k, kind in kinds.items() if k != "cost" or lut is not None}
+        lut = None if lut is None else side.put(lut)
+        side.call(self.L.tsl_tsdf_nav_terrain, self.L.tsl_tsdf_nav_terrain_dev, self.h, C.byref(cfg), side.ptr(lut), *(side.ptr(pl.get(k)) for k in kinds))
         out.update(pl)
         return out
 
@@ -1557,12 +1475,8 @@ class DenseTSDF(BaseMap):
         r, t = _dptr(R, 9)[1], _dptr(T, 3)[1]
         Ro, To, ro, to = _pose_out()
         rep = _lib.TrackReport()
-        if on_dev:
-            torch = _torch()
-            _lib.check(self.L.tsl_tsdf_track_depth_dev(self.h, r, t, C.byref(cfg), C.byref(tc), ptr, ro, to, C.byref(rep),
-                                                       torch.cuda.current_stream(keep.device).cuda_stream))
-        else:
-            _lib.check(self.L.tsl_tsdf_track_depth(self.h, r, t, C.byref(cfg), C.byref(tc), ptr, ro, to, C.byref(rep)))
+        side = device_side(keep.device) if on_dev else HOST
+        side.call(self.L.tsl_tsdf_track_depth, self.L.tsl_tsdf_track_depth_dev, self.h, r, t, C.byref(cfg), C.byref(tc), ptr, ro, to, C.byref(rep))
         return Ro.reshape(3, 3), To, _track_info(rep)
 
     # ---- scan-to-model alignment (tsl_align_points.hip) -------------------------------------------
@@ -1612,12 +1526,8 @@ class DenseTSDF(BaseMap):
         r, t = _dptr(R, 9)[1], _dptr(T, 3)[1]
         Ro, To, ro, to = _pose_out()
         rep = _lib.TrackReport()
-        if on_dev:
-            torch = _torch()
-            _lib.check(self.L.tsl_tsdf_track_points_dev(self.h, r, t, C.byref(cfg), C.byref(tc), ptr, n, ro, to, C.byref(rep),
-                                                        torch.cuda.current_stream(keep.device).cuda_stream))
-        else:
-            _lib.check(self.L.tsl_tsdf_track_points(self.h, r, t, C.byref(cfg), C.byref(tc), ptr, n, ro, to, C.byref(rep)))
+        side = device_side(keep.device) if on_dev else HOST
+        side.call(self.L.tsl_tsdf_track_points, self.L.tsl_tsdf_track_points_dev, self.h, r, t, C.byref(cfg), C.byref(tc), ptr, n, ro, to, C.byref(rep))
         return Ro.reshape(3, 3), To, _track_info(rep)
 
     # ---- map-to-map registration (tsl_register.hip) -------------------------------------------------
@@ -1778,27 +1688,21 @@ class DenseTSDF(BaseMap):
         if gradient and not mode:
             raise ValueError("query_esdf: the gradient needs interpolate=True")
         if refresh:
-            if not getattr(self, "_esdf_ever", False):
-                raise _lib.TslError("query_esdf: call update_esdf first (refresh repeats the last update's parameters)")
-            self.update_esdf(gamma=self._esdf_gamma, max_dist=self._esdf_max_dist, wait=False)
-        if _is_device_tensor(xyz):
-            torch = _torch()
-            x = xyz.reshape(-1, 3).contiguous().float()
-            n = x.shape[0]
-            dist = torch.empty(n, dtype=torch.float32, device=x.device)
-            grad = torch.empty((n, 3), dtype=torch.float32, device=x.device) if gradient else None
-            status = torch.empty(n, dtype=torch.uint8, device=x.device)
-            _lib.check(self.L.tsl_esdf_query_points_dev(self.h, mode, float(unknown_value), x.data_ptr(), n, dist.data_ptr(),
-                                                        None if grad is None else grad.data_ptr(), status.data_ptr(),
-                                                        torch.cuda.current_stream(x.device).cuda_stream))
-            return dist, grad, status
-        x = np.ascontiguousarray(np.asarray(xyz, dtype=np.float32).reshape(-1, 3))
+            self._esdf_refresh("query_esdf")
+        x, side = _points_f32(xyz)
         n = x.shape[0]
-        dist = np.empty(n, np.float32)
-        grad = np.empty((n, 3), np.float32) if gradient else None
-        status = np.empty(n, np.uint8)
-        _lib.check(self.L.tsl_esdf_query_points(self.h, mode, float(unknown_value), _vp(x), n, _vp(dist), _vp(grad), _vp(status)))
+        dist = side.out(n, "f4")
+        grad = side.out((n, 3), "f4") if gradient else None
+        status = side.out(n, "u1")
+        side.call(self.L.tsl_esdf_query_points, self.L.tsl_esdf_query_points_dev, self.h, mode, float(unknown_value), side.ptr(x), n, side.ptr(dist),
+                  side.ptr(grad), side.ptr(status))
         return dist, grad, status
+
+    def _esdf_refresh(self, who):
+        """refresh=True of the ESDF's readers: an ESDF must exist, and an incremental update with the parameters of the last update_esdf is queued"""
+        if not getattr(self, "_esdf_ever", False):
+            raise _lib.TslError(f"{who}: call update_esdf first (refresh repeats the last update's parameters)")
+        self.update_esdf(gamma=self._esdf_gamma, max_dist=self._esdf_max_dist, wait=False)
 
     def score_paths(self, waypoints, radius, margin=0.0, sub=1, lengths=None, interpolate=True, stop=False, unknown_blocks=True, outside_blocks=True,
                     samples=False, unknown_value=float("nan"), refresh=True):
@@ -1820,107 +1724,25 @@ class DenseTSDF(BaseMap):
         if int(sub) < 1:
             raise ValueError("score_paths: sub must be at least 1")
         if refresh:
-            if not getattr(self, "_esdf_ever", False):
-                raise _lib.TslError("score_paths: call update_esdf first (refresh repeats the last update's parameters)")
-            self.update_esdf(gamma=self._esdf_gamma, max_dist=self._esdf_max_dist, wait=False)
-        if _is_device_tensor(waypoints):
-            torch = _torch()
-            w = waypoints.reshape((-1,) + tuple(waypoints.shape[-2:])).contiguous().float()
-            if w.dim() != 3 or w.shape[2] != 3:
-                raise ValueError("score_paths: waypoints must be [n, K, 3] or [K, 3]")
-            n, K = int(w.shape[0]), int(w.shape[1])
-            ln = None
-            if lengths is not None:
-                if not _is_device_tensor(lengths) or lengths.dtype != torch.int32:
-                    raise TypeError("score_paths: with torch waypoints, lengths must be a torch.int32 tensor on the same device")
-                ln = lengths.reshape(-1).contiguous()
-                if ln.shape[0] != n:
-                    raise ValueError("score_paths: one length per path")
-            smax = (K - 1) * int(sub) + 1
-            rec = torch.empty((n, 10), dtype=torch.int32, device=w.device)
-            sd = torch.empty((n, smax), dtype=torch.float32, device=w.device) if samples else None
-            ss = torch.empty((n, smax), dtype=torch.uint8, device=w.device) if samples else None
-            _lib.check(self.L.tsl_esdf_score_paths_dev(self.h, mode, float(unknown_value), w.data_ptr(), None if ln is None else ln.data_ptr(), n, K, int(sub),
-                                                       float(radius), float(margin), flags, rec.data_ptr(), None if sd is None else sd.data_ptr(),
-                                                       None if ss is None else ss.data_ptr(), torch.cuda.current_stream(w.device).cuda_stream))
-            out = {k: rec[:, i] for i, k in enumerate(PATH_SCORE_DTYPE.names[:8])}
-            out["min_dist"] = rec[:, 6].view(torch.float32)
-            out["cost"] = rec[:, 8:10].contiguous().view(torch.int64).reshape(n)
-        else:
-            w = np.asarray(waypoints, dtype=np.float32)
-            if w.ndim == 2:
-                w = w[None]
-            if w.ndim != 3 or w.shape[2] != 3:
-                raise ValueError("score_paths: waypoints must be [n, K, 3] or [K, 3]")
-            w = np.ascontiguousarray(w)
-            n, K = w.shape[0], w.shape[1]
-            ln = None
-            if lengths is not None:
-                ln = np.asarray(lengths)
-                if not np.issubdtype(ln.dtype, np.integer):
-                    raise TypeError("score_paths: lengths must be integers")
-                if ln.shape != (n,):
-                    raise ValueError("score_paths: one length per path")
-                if n and (ln.min() < 1 or ln.max() > K):
-                    raise ValueError("score_paths: a length outside 1 .. K")
-                ln = np.ascontiguousarray(ln, dtype=np.int32)
-            smax = (K - 1) * int(sub) + 1
-            rec = np.zeros(n, PATH_SCORE_DTYPE)
-            sd = np.empty((n, smax), np.float32) if samples else None
-            ss = np.empty((n, smax), np.uint8) if samples else None
-            _lib.check(self.L.tsl_esdf_score_paths(self.h, mode, float(unknown_value), _vp(w), _vp(ln), n, K, int(sub), float(radius), float(margin), flags,
-                                                   _vp(rec), _vp(sd), _vp(ss)))
-            out = {k: rec[k].copy() for k in PATH_SCORE_DTYPE.names}
+            self._esdf_refresh("score_paths")
+        w, ln, side, _ = _polylines("score_paths", waypoints, lengths, 1, "path", "waypoints")
+        n, K = int(w.shape[0]), int(w.shape[1])
+        smax = (K - 1) * int(sub) + 1
+        rec = side.out((n, PATH_SCORE_DTYPE.itemsize // 4), "i4")
+        sd = side.out((n, smax), "f4") if samples else None
+        ss = side.out((n, smax), "u1") if samples else None
+        side.call(self.L.tsl_esdf_score_paths, self.L.tsl_esdf_score_paths_dev, self.h, mode, float(unknown_value), side.ptr(w), side.ptr(ln), n, K, int(sub),
+                  float(radius), float(margin), flags, side.ptr(rec), side.ptr(sd), side.ptr(ss))
+        out = record_columns(rec, PATH_SCORE_DTYPE)
         if samples:
             out["sample_dist"], out["sample_status"] = sd, ss
         return out
 
     def _traj_inputs(self, who, ctrl, lengths, refresh):
-        """(ctrl [n, K, 3] f32 contiguous, lengths int32 [n] or None, on the device?, one trajectory?) of traj_linearize / traj_optimize"""
+        """(ctrl [n, K, 3] f32 contiguous, lengths int32 [n] or None, the side, one trajectory?) of traj_linearize / traj_optimize"""
         if refresh:
-            if not getattr(self, "_esdf_ever", False):
-                raise _lib.TslError(f"{who}: call update_esdf first (refresh repeats the last update's parameters)")
-            self.update_esdf(gamma=self._esdf_gamma, max_dist=self._esdf_max_dist, wait=False)
-        dev = _is_device_tensor(ctrl)
-        if dev:
-            torch = _torch()
-            one = ctrl.dim() == 2
-            c = (ctrl[None] if one else ctrl).contiguous().float()
-        else:
-            c = np.asarray(ctrl, dtype=np.float32)
-            one = c.ndim == 2
-            c = np.ascontiguousarray(c[None] if one else c)
-        if c.ndim != 3 or c.shape[2] != 3:
-            raise ValueError(f"{who}: ctrl must be [n, K, 3] or [K, 3]")
-        n, K = int(c.shape[0]), int(c.shape[1])
-        ln = None
-        if lengths is not None and dev:
-            if not _is_device_tensor(lengths) or lengths.dtype != torch.int32:
-                raise TypeError(f"{who}: with torch ctrl, lengths must be a torch.int32 tensor on the same device")
-            ln = lengths.reshape(-1).contiguous()
-            if ln.shape[0] != n:
-                raise ValueError(f"{who}: one length per trajectory")
-        elif lengths is not None:
-            ln = np.asarray(lengths)
-            if not np.issubdtype(ln.dtype, np.integer):
-                raise TypeError(f"{who}: lengths must be integers")
-            if ln.shape != (n,):
-                raise ValueError(f"{who}: one length per trajectory")
-            if n and (ln.min() < 4 or ln.max() > K):
-                raise ValueError(f"{who}: a length outside 4 .. K")
-            ln = np.ascontiguousarray(ln, dtype=np.int32)
-        return c, ln, dev, one
-
-    @staticmethod
-    def _traj_record(rec, dev):
-        if not dev:
-            return {k: rec[k].copy() for k in TRAJ_SCORE_DTYPE.names}
-        torch = _torch()
-        out = {k: rec[:, i] for i, k in enumerate(TRAJ_SCORE_DTYPE.names[:8])}
-        out["min_dist"] = rec[:, 5].view(torch.float32)
-        out["cost_collision"] = rec[:, 8:10].contiguous().view(torch.int64).reshape(-1)
-        out["cost_smooth"] = rec[:, 10:12].contiguous().view(torch.int64).reshape(-1)
-        return out
+            self._esdf_refresh(who)
+        return _polylines(who, ctrl, lengths, 4, "trajectory", "ctrl")
 
     def traj_linearize(self, ctrl, clearance, sub=4, lengths=None, gradients=True, unknown_value=float("nan"), refresh=True):
         """The collision and smoothness costs of uniform cubic B-spline trajectories against the ESDF, with their gradients over the control points, in
@@ -1933,23 +1755,14 @@ class DenseTSDF(BaseMap):
         grad_smooth, int64 [n, K, 3] in units of 2^-20 m.  Every field is exact and independent of the schedule.  numpy in -> numpy out; torch CUDA
         tensors in (lengths then a torch.int32 tensor) -> torch tensors, asynchronously, ordered with torch.cuda.current_stream.  refresh as in
         query_esdf."""
-        c, ln, dev, _ = self._traj_inputs("traj_linearize", ctrl, lengths, refresh)
+        c, ln, side, _ = self._traj_inputs("traj_linearize", ctrl, lengths, refresh)
         n, K = int(c.shape[0]), int(c.shape[1])
-        if dev:
-            torch = _torch()
-            rec = torch.empty((n, 12), dtype=torch.int32, device=c.device)
-            gc = torch.empty((n, K, 3), dtype=torch.int64, device=c.device) if gradients else None
-            gs = torch.empty((n, K, 3), dtype=torch.int64, device=c.device) if gradients else None
-            ptr = lambda t: None if t is None else t.data_ptr()
-            _lib.check(self.L.tsl_esdf_traj_linearize_dev(self.h, float(unknown_value), c.data_ptr(), ptr(ln), n, K, int(sub), float(clearance), rec.data_ptr(),
-                                                          ptr(gc), ptr(gs), torch.cuda.current_stream(c.device).cuda_stream))
-        else:
-            rec = np.zeros(n, TRAJ_SCORE_DTYPE)
-            gc = np.zeros((n, K, 3), np.int64) if gradients else None
-            gs = np.zeros((n, K, 3), np.int64) if gradients else None
-            _lib.check(self.L.tsl_esdf_traj_linearize(self.h, float(unknown_value), _vp(c), _vp(ln), n, K, int(sub), float(clearance), _vp(rec), _vp(gc),
-                                                      _vp(gs)))
-        out = self._traj_record(rec, dev)
+        rec = side.out((n, TRAJ_SCORE_DTYPE.itemsize // 4), "i4")
+        gc = side.out((n, K, 3), "i8") if gradients else None
+        gs = side.out((n, K, 3), "i8") if gradients else None
+        side.call(self.L.tsl_esdf_traj_linearize, self.L.tsl_esdf_traj_linearize_dev, self.h, float(unknown_value), side.ptr(c), side.ptr(ln), n, K, int(sub),
+                  float(clearance), side.ptr(rec), side.ptr(gc), side.ptr(gs))
+        out = record_columns(rec, TRAJ_SCORE_DTYPE)
         if gradients:
             out["grad_collision"], out["grad_smooth"] = gc, gs
         return out
@@ -1965,25 +1778,17 @@ class DenseTSDF(BaseMap):
         ([K, 3] for one trajectory); history=True adds history int64 [n, iters + 1, 2], (cost_collision, cost_smooth) of every linearisation and -1
         behind a stop.  Samples that are unknown or outside pull nowhere: check n_unknown and n_outside, or re-check the result with
         score_paths(bspline_points(ctrl, sub), clearance).  Arrays in and out as in traj_linearize."""
-        c, ln, dev, one = self._traj_inputs("traj_optimize", ctrl, lengths, refresh)
+        c, ln, side, one = self._traj_inputs("traj_optimize", ctrl, lengths, refresh)
         n, K = int(c.shape[0]), int(c.shape[1])
         o = _lib.TrajOpt(clearance=float(clearance), w_collision=float(w_collision), w_smooth=float(w_smooth), step=float(step), momentum=float(momentum),
                          max_move=0.5 * float(self.voxel_scale) if max_move is None else float(max_move), sub=int(sub), iters=int(iters),
                          fix_head=int(fix_ends), fix_tail=int(fix_ends), flags=1 if stop_when_free else 0)
-        if dev:
-            torch = _torch()
-            rec = torch.empty((n, 12), dtype=torch.int32, device=c.device)
-            co = torch.empty_like(c)
-            hist = torch.empty((n, max(o.iters, 0) + 1, 2), dtype=torch.int64, device=c.device) if history else None
-            _lib.check(self.L.tsl_esdf_traj_optimize_dev(self.h, float(unknown_value), c.data_ptr(), None if ln is None else ln.data_ptr(), n, K, C.byref(o),
-                                                         co.data_ptr(), rec.data_ptr(), None if hist is None else hist.data_ptr(),
-                                                         torch.cuda.current_stream(c.device).cuda_stream))
-        else:
-            rec = np.zeros(n, TRAJ_SCORE_DTYPE)
-            co = np.zeros_like(c)
-            hist = np.zeros((n, max(o.iters, 0) + 1, 2), np.int64) if history else None
-            _lib.check(self.L.tsl_esdf_traj_optimize(self.h, float(unknown_value), _vp(c), _vp(ln), n, K, C.byref(o), _vp(co), _vp(rec), _vp(hist)))
-        out = self._traj_record(rec, dev)
+        rec = side.out((n, TRAJ_SCORE_DTYPE.itemsize // 4), "i4")
+        co = side.out((n, K, 3), "f4")
+        hist = side.out((n, max(o.iters, 0) + 1, 2), "i8") if history else None
+        side.call(self.L.tsl_esdf_traj_optimize, self.L.tsl_esdf_traj_optimize_dev, self.h, float(unknown_value), side.ptr(c), side.ptr(ln), n, K, C.byref(o),
+                  side.ptr(co), side.ptr(rec), side.ptr(hist))
+        out = record_columns(rec, TRAJ_SCORE_DTYPE)
         out["ctrl"] = co[0] if one else co
         if history:
             out["history"] = hist

@@ -7,12 +7,9 @@ import time
 import numpy as np
 
 from .. import _lib
+from ._sides import _vp
 from .fields import DeviceArrayField, MapFieldRef, ScalarField
 from .mapping_common import BaseMap, _dptr
-
-
-def _vp(a):
-    return None if a is None else a.ctypes.data_as(C.c_void_p)
 
 
 class Octomap(BaseMap):

@@ -18,14 +18,11 @@ import ctypes as C
 import numpy as np
 
 from .. import _lib
+from ._sides import _vp, device_side
 from .fields import ScalarField, device_view
 
 MAX_MAP_NODE = 4096
 F32 = np.float32
-
-
-def _vp(a):
-    return None if a is None else a.ctypes.data_as(C.c_void_p)
 
 
 def _dot(a, b):
@@ -155,12 +152,10 @@ class TopoGraphGen:
         assert p.shape == d.shape and p.is_cuda and d.is_cuda
         n = p.shape[0]
         sk = None if skip_idx is None else skip_idx.reshape(-1).contiguous().to(torch.int32)
-        hit = torch.empty(n, dtype=torch.uint8, device=p.device); typ = torch.empty(n, dtype=torch.uint8, device=p.device)
-        end = torch.empty((n, 3), dtype=torch.float32, device=p.device); ln = torch.empty(n, dtype=torch.float32, device=p.device)
-        poly = torch.empty(n, dtype=torch.int32, device=p.device)
-        _lib.check(self.L.tsl_topo_rays_dev(self.h, p.data_ptr(), d.data_ptr(), None if sk is None else sk.data_ptr(), n, float(F32(max_dist)), float(F32(backward)),
-                                            1 if facelets_only else 0, hit.data_ptr(), typ.data_ptr(), end.data_ptr(), ln.data_ptr(), poly.data_ptr(),
-                                            torch.cuda.current_stream(p.device).cuda_stream))
+        side = device_side(p.device)
+        hit, typ, end, ln, poly = side.out(n, "u1"), side.out(n, "u1"), side.out((n, 3), "f4"), side.out(n, "f4"), side.out(n, "i4")
+        side.call(self.L.tsl_topo_rays, self.L.tsl_topo_rays_dev, self.h, side.ptr(p), side.ptr(d), side.ptr(sk), n, float(F32(max_dist)), float(F32(backward)),
+                  1 if facelets_only else 0, side.ptr(hit), side.ptr(typ), side.ptr(end), side.ptr(ln), side.ptr(poly))
         return hit.bool(), typ, end, ln, poly
 
     def detect_collisions(self, start_pt):
