@@ -71,6 +71,8 @@ enum { TSL_K_VOXELIZE = 0, TSL_K_SORT = 1, TSL_K_RAYS = 2, TSL_K_INTEGRATE = 3, 
        TSL_K_NAV_FIELD_SEED = 24, TSL_K_NAV_FIELD_ROUND = 25, TSL_K_NAV_FIELD_PARENT = 26, TSL_K_NAV_FIELD_PATHS = 27,
        TSL_K_NAV_TERRAIN_COLUMNS = 28, TSL_K_NAV_TERRAIN_WINDOW = 29,
        TSL_K_COUNT };
+/* the ids added since: the first enum ends where it always did, prof_query takes every id below TSL_K_END */
+enum { TSL_K_ALIGN_RGBD = 30, TSL_K_END = 31 };
 
 const char* tsl_version(void);
 const char* tsl_last_error(void);
@@ -487,6 +489,57 @@ int  tsl_tsdf_track_depth(tsl_tsdf* m, const double R0[9], const double T0[3], c
                           double R_out[9], double T_out[3], tsl_track_report* rep);
 int  tsl_tsdf_track_depth_dev(tsl_tsdf* m, const double R0[9], const double T0[3], const tsl_align_cfg* c, const tsl_track_cfg* t, const void* depth_dev,
                               double R_out[9], double T_out[3], tsl_track_report* rep, void* user_stream);
+
+/* ---- depth-and-colour alignment (tsl_align_rgbd.hip): the problem of the section above with a second residual, the
+ * luminance the textured map stores at the warped pixel minus the luminance of the image (Bylow, Olsson, Kahl, "Robust camera tracking by combining
+ * color and depth measurements", ICPR 2014).  Signed distance says nothing in the directions in which the geometry does not change (a flat wall
+ * leaves three degrees of freedom, a corridor one); the texture of the surface does.  The map must be textured (texture_enabled).
+ * depth: uint16 millimetres [h][w]; rgb: uint8 [h][w][3], registered to the depth image (the same h, w and intrinsics), both C-contiguous.
+ * Definition (all f32, no contraction, in this order).  The visited pixels, the depth gate, the back-projection, p, the KNOWN test, s and g are
+ * those of tsl_tsdf_align_linearize, and the GEOMETRIC sums (geo) are exactly its 33 integers.
+ *   voxel luminance   yv = ((77 * r + 150 * g) + 29 * b) / 256 of the three stored f16 channels converted to f32
+ *   image luminance   yi = (float)(77 * R + 150 * G + 29 * B) / 65280.0f (the integer is exact)
+ *   map luminance     Y = the trilinear interpolant and gY = its gradient per metre of the eight yv, over the same eight corners and with the
+ *                     same cell fractions as s (a KNOWN cell of a textured map has all eight)
+ * The COLOUR sums (col) are a second tsl_align_sums; every visited pixel lands in exactly one of its buckets, tested in this order:
+ *   n_gate     the geometric gate
+ *   n_unknown  the geometric unknown
+ *   n_far      not |s| <= r_max (off the surface, where the colour means nothing), or rc = Y - yi is not |rc| <= rc_max (a NaN is far)
+ *   n_grad     (gY0 * gY0 + gY1 * gY1) + gY2 * gY2 is not in (0, gc_max * gc_max]
+ *   n_used     J = (gY, p x gY), wgt = huber_c > 0 && |rc| > huber_c ? huber_c / |rc| : 1 and the 28 products of the section above with rc in place
+ *              of s, each added as rint(x * 2^20)
+ * The colour buckets do not depend on the geometric n_grad.  A stored colour that is not finite (tsl_tsdf_import_sparse writes any bit pattern)
+ * makes Y or gY of its cells a NaN or an inf: such a sample is colour-far or colour-grad, no such value reaches a product, and the geometric half is
+ * untouched.
+ * tsl_align_rgbd_cfg: a (tsl_align_cfg: everything of the section above, flags bit 0 = counts only for both halves), rc_max (0 = 1), gc_max (0 =
+ * 1 / voxel, formed once in f32), huber_c (0 = off).  Each half has its own overflow refusal: the geometric bound as it stands, and
+ * Mc^2 * 2^20 * visited <= 2^62 with Mc = max(2 L gc_max, gc_max, rc_max).
+ * tsl_tsdf_align_rgbd_linearize issues the queued frames, runs on the handle's stream, waits and returns the 66 integers.  The device form is
+ * ASYNCHRONOUS like tsl_tsdf_align_linearize_dev, with its stream ordering: sums_dev is int64[80], geo in [0, 33), col in [40, 73), the rest 0.
+ * Step (pure host, float64, fixed order): Hd = Hg * 2^-20 + lambda * (Hc * 2^-20), bd likewise; then the damping, the Cholesky factorisation and
+ * the solution of tsl_align_solve.  With lambda = 0 the step equals tsl_align_solve on the geometric half bit for bit.
+ * Tracking iterates as tsl_tsdf_track_depth does, with the same tsl_track_cfg, statuses and returned pose.  lambda >= 0 is the weight of the
+ * colour term; lambda < 0 means automatic: at the first linearisation of the track lambda = balance * (Hg_00 + Hg_11 + Hg_22) / (Hc_00 + Hc_11 +
+ * Hc_22), from the integers converted to float64 and added in this order, 0 when the denominator is 0 (an untextured view falls back to pure
+ * geometry) -- the two terms are then equally stiff in translation.  The value is held for the whole call and returned in the report (0 when
+ * nothing was linearised).  A track is lost when the GEOMETRIC n_used < min_used (0 = 6): colour alone does not fix depth.
+ * With profiling on, tsl_tsdf_prof_query(m, TSL_K_ALIGN_RGBD) returns the time of the kernel alone.
+ * TSL_ERR_ARG before anything is launched: everything tsl_tsdf_align_linearize refuses, a null rgb, an untextured map, a negative or non-finite
+ * rc_max / gc_max / huber_c / balance, a non-finite lambda (tsl_align_rgbd_solve: a negative one too), either overflow bound. */
+typedef struct { tsl_align_cfg a; float rc_max, gc_max, huber_c; } tsl_align_rgbd_cfg;
+typedef struct { tsl_align_sums geo, col; } tsl_align_rgbd_sums;
+typedef struct { double R[9], T[3], xi[6]; tsl_align_rgbd_sums sums; } tsl_track_rgbd_iter;
+typedef struct { int32_t status, iterations; double lambda; tsl_track_rgbd_iter it[64]; } tsl_track_rgbd_report;
+int  tsl_tsdf_align_rgbd_linearize(tsl_tsdf* m, const double R[9], const double T[3], const tsl_align_rgbd_cfg* c, const uint16_t* depth,
+                                   const uint8_t* rgb, tsl_align_rgbd_sums* out);
+int  tsl_tsdf_align_rgbd_linearize_dev(tsl_tsdf* m, const double R[9], const double T[3], const tsl_align_rgbd_cfg* c, const void* depth_dev,
+                                       const void* rgb_dev, void* sums_dev, void* user_stream);
+int  tsl_align_rgbd_solve(const tsl_align_rgbd_sums* s, double lambda, double damping, double xi[6], int32_t* singular);
+int  tsl_tsdf_track_rgbd(tsl_tsdf* m, const double R0[9], const double T0[3], const tsl_align_rgbd_cfg* c, const tsl_track_cfg* t, double lambda,
+                         double balance, const uint16_t* depth, const uint8_t* rgb, double R_out[9], double T_out[3], tsl_track_rgbd_report* rep);
+int  tsl_tsdf_track_rgbd_dev(tsl_tsdf* m, const double R0[9], const double T0[3], const tsl_align_rgbd_cfg* c, const tsl_track_cfg* t, double lambda,
+                             double balance, const void* depth_dev, const void* rgb_dev, double R_out[9], double T_out[3], tsl_track_rgbd_report* rep,
+                             void* user_stream);
 
 /* ---- scan-to-model alignment (tsl_align_points.hip): a point cloud against the TSDF -- the problem of the section above for sensors whose data is
  * no pinhole image (a spinning or solid-state lidar, a merged multi-camera cloud, an undistorted depth image): minimise the sum of s(R p_i + T)^2

@@ -12,13 +12,14 @@ K_VIEW_GAIN, K_ALIGN, K_ALIGN_POINTS, K_PATH_SCORE = 17, 18, 19, 20
 K_NAV_PROJECT, K_NAV_EDT, K_NAV_EDT_ROWS = 21, 22, 23
 K_NAV_FIELD_SEED, K_NAV_FIELD_ROUND, K_NAV_FIELD_PARENT, K_NAV_FIELD_PATHS = 24, 25, 26, 27
 K_NAV_TERRAIN_COLUMNS, K_NAV_TERRAIN_WINDOW = 28, 29
+K_ALIGN_RGBD = 30
 KERNEL_NAMES = {K_VOXELIZE: "voxelize", K_SORT: "sort", K_RAYS: "build_rays", K_INTEGRATE: "integrate",
                 K_FINALIZE: "finalize", K_MESH: "marching_cubes", K_SEGMENTS: "segments", K_BIN: "bin", K_ESDF: "esdf", K_FUSE: "fuse", K_REGISTER: "register",
                 K_REGISTER_SCORE: "register_score", K_FRONTIER_MARK: "frontier_mark", K_FRONTIER_LABEL: "frontier_label", K_FRONTIER_JOIN: "frontier_join",
                 K_FRONTIER_SUM: "frontier_sum", K_FRONTIER_EMIT: "frontier_emit", K_VIEW_GAIN: "view_gain", K_ALIGN: "align", K_ALIGN_POINTS: "align_points",
                 K_PATH_SCORE: "path_score", K_NAV_PROJECT: "nav_project", K_NAV_EDT: "nav_edt", K_NAV_EDT_ROWS: "nav_edt_rows",
                 K_NAV_FIELD_SEED: "nav_field_seed", K_NAV_FIELD_ROUND: "nav_field_round", K_NAV_FIELD_PARENT: "nav_field_parent",
-                K_NAV_FIELD_PATHS: "nav_field_paths", K_NAV_TERRAIN_COLUMNS: "nav_terrain_columns", K_NAV_TERRAIN_WINDOW: "nav_terrain_window"}
+                K_NAV_FIELD_PATHS: "nav_field_paths", K_NAV_TERRAIN_COLUMNS: "nav_terrain_columns", K_NAV_TERRAIN_WINDOW: "nav_terrain_window", K_ALIGN_RGBD: "align_rgbd"}
 
 
 class TsdfCfg(C.Structure):
@@ -102,6 +103,24 @@ class TrackIter(C.Structure):
 
 class TrackReport(C.Structure):
     _fields_ = [("status", C.c_int32), ("iterations", C.c_int32), ("it", TrackIter * 64)]
+
+
+class AlignRgbdCfg(C.Structure):
+    """tsl_align_rgbd_cfg (tsl_tsdf_align_rgbd_linearize, tsl_tsdf_track_rgbd): a tsl_align_cfg and the colour gates; a zero rc_max / gc_max means the default, huber_c 0 = off"""
+    _fields_ = [("a", AlignCfg), ("rc_max", C.c_float), ("gc_max", C.c_float), ("huber_c", C.c_float)]
+
+
+class AlignRgbdSums(C.Structure):
+    """tsl_align_rgbd_sums: the geometric and the colour tsl_align_sums, 66 x int64"""
+    _fields_ = [("geo", AlignSums), ("col", AlignSums)]
+
+
+class TrackRgbdIter(C.Structure):
+    _fields_ = [("R", C.c_double * 9), ("T", C.c_double * 3), ("xi", C.c_double * 6), ("sums", AlignRgbdSums)]
+
+
+class TrackRgbdReport(C.Structure):
+    _fields_ = [("status", C.c_int32), ("iterations", C.c_int32), ("lam", C.c_double), ("it", TrackRgbdIter * 64)]
 
 
 class RegisterScore(C.Structure):
@@ -332,6 +351,12 @@ SIGNATURES = {
     "tsl_pose_retract": (C.c_int, [dp, dp, dp]),
     "tsl_tsdf_track_depth": (C.c_int, [vp, dp, dp, C.POINTER(AlignCfg), C.POINTER(TrackCfg), vp, dp, dp, C.POINTER(TrackReport)]),
     "tsl_tsdf_track_depth_dev": (C.c_int, [vp, dp, dp, C.POINTER(AlignCfg), C.POINTER(TrackCfg), vp, dp, dp, C.POINTER(TrackReport), vp]),
+    "tsl_tsdf_align_rgbd_linearize": (C.c_int, [vp, dp, dp, C.POINTER(AlignRgbdCfg), vp, vp, C.POINTER(AlignRgbdSums)]),
+    "tsl_tsdf_align_rgbd_linearize_dev": (C.c_int, [vp, dp, dp, C.POINTER(AlignRgbdCfg), vp, vp, vp, vp]),
+    "tsl_align_rgbd_solve": (C.c_int, [C.POINTER(AlignRgbdSums), C.c_double, C.c_double, dp, pi32]),
+    "tsl_tsdf_track_rgbd": (C.c_int, [vp, dp, dp, C.POINTER(AlignRgbdCfg), C.POINTER(TrackCfg), C.c_double, C.c_double, vp, vp, dp, dp, C.POINTER(TrackRgbdReport)]),
+    "tsl_tsdf_track_rgbd_dev": (C.c_int, [vp, dp, dp, C.POINTER(AlignRgbdCfg), C.POINTER(TrackCfg), C.c_double, C.c_double, vp, vp, dp, dp,
+                                          C.POINTER(TrackRgbdReport), vp]),
     "tsl_tsdf_align_points_linearize": (C.c_int, [vp, dp, dp, C.POINTER(AlignPointsCfg), vp, C.c_int64, C.POINTER(AlignSums), vp, vp]),
     "tsl_tsdf_align_points_linearize_dev": (C.c_int, [vp, dp, dp, C.POINTER(AlignPointsCfg), vp, C.c_int64, vp, vp, vp, vp]),
     "tsl_tsdf_track_points": (C.c_int, [vp, dp, dp, C.POINTER(AlignPointsCfg), C.POINTER(TrackCfg), vp, C.c_int64, dp, dp, C.POINTER(TrackReport)]),

@@ -1,4 +1,5 @@
 // tsl_align_common.hpp -- the one copy of what the Gauss-Newton family shares: the frame-to-model alignment (tsl_align.hip), the
+// depth-and-colour alignment (tsl_align_rgbd.hip, section 4.8.2: al_sample_lum, al_solve_rgbd, al_iterate_with over its 66 integers), the
 // map-to-map registration (tsl_register.hip, section 4.9) and the pose scoring (tsl_register_search.hip, section 4.10).  Device side, the bit-exact
 // contract that tests/track_ref.py restates (points, robust_weight): al_sample carries a map-frame point into its bucket, al_weight is the robust
 // weight, al_products adds the 28 fixed-point products of a used sample, al_flush reduces them over the workgroup (the halving butterfly, LDS, one
@@ -58,6 +59,36 @@ __device__ __forceinline__ int al_sample(const float p[3], const MapDev& M, cons
     return (gg > 0.0f && gg <= gm2) ? AL_USED : AL_GRAD;          // a NaN or inf gradient is grad: no value that is not finite reaches a product
 }
 
+// al_sample over a textured map with the colour bucket beside the geometric one (the return value, exactly al_sample's): *cb is AL_UNKNOWN, AL_FAR,
+// AL_GRAD or AL_USED in the order of DESIGN.md section 4.8.2, and for a colour-used sample *rc = Y - yi and gY is the luminance gradient per metre.
+// yi: the luminance of the pixel; gcm2 = gc_max * gc_max.  The colour bucket does not depend on the geometric AL_GRAD.
+__device__ __forceinline__ int al_sample_lum(const float p[3], const MapDev& M, const int* __restrict__ T, float vs, float r_max, float gm2, float yi, float rc_max,
+                                             float gcm2, float* s, float g[3], int* cb, float* rc, float gY[3])
+{
+    float u[3]; int b[3];
+#pragma unroll
+    for (int a = 0; a < 3; ++a) { u[a] = p[a] / vs; b[a] = cell_floor(u[a]); }
+    float V[8], Y[8];
+    *cb = AL_UNKNOWN;
+    if (!(isfinite(p[0]) && isfinite(p[1]) && isfinite(p[2]) && tsdf_read_cell_lum(M, T, b[0], b[1], b[2], V, Y))) return AL_UNKNOWN;
+    const float f0 = u[0] - (float)b[0], f1 = u[1] - (float)b[1], f2 = u[2] - (float)b[2];
+    *s = tri_value(V, f0, f1, f2);
+    *cb = AL_FAR;
+    if (!(fabsf(*s) <= r_max)) return AL_FAR;                     // off the surface the colour means nothing
+    tri_grad(V, f0, f1, f2, &g[0], &g[1], &g[2]);
+    g[0] = g[0] / vs; g[1] = g[1] / vs; g[2] = g[2] / vs;
+    const float gg = (g[0] * g[0] + g[1] * g[1]) + g[2] * g[2];
+    const int bucket = (gg > 0.0f && gg <= gm2) ? AL_USED : AL_GRAD;
+    *rc = tri_value(Y, f0, f1, f2) - yi;
+    if (fabsf(*rc) <= rc_max) {                                   // a NaN residual (a stored colour that is not finite) is far
+        tri_grad(Y, f0, f1, f2, &gY[0], &gY[1], &gY[2]);
+        gY[0] = gY[0] / vs; gY[1] = gY[1] / vs; gY[2] = gY[2] / vs;
+        const float cg = (gY[0] * gY[0] + gY[1] * gY[1]) + gY[2] * gY[2];
+        *cb = (cg > 0.0f && cg <= gcm2) ? AL_USED : AL_GRAD;
+    }
+    return bucket;
+}
+
 // the robust weight of the residual r
 __device__ __forceinline__ float al_weight(float r, float huber)
 {
@@ -84,7 +115,7 @@ __device__ __forceinline__ void al_products(const float p[3], const float g[3], 
 }
 
 // The end of a linearisation kernel of 256 threads: the sums v of every lane and the five counts of every wave (uniform in the wave) are added into
-// acc[0 .. 32].  reduce: some lane of this wave holds products (it used a sample and the sums are wanted); otherwise v is zero and the butterfly is
+// acc[0 .. 32].  A kernel that flushes twice (tsl_align_rgbd.hip) puts a barrier between the calls: they share this LDS.  reduce: some lane of this wave holds products (it used a sample and the sums are wanted); otherwise v is zero and the butterfly is
 // left out.  After the five halving steps lane l holds sum number l >> 1 over its half of the wave, the last step adds the other half.
 __device__ __forceinline__ void al_flush(long long (&v)[32], int n_used, int n_gate, int n_unknown, int n_far, int n_grad, bool reduce, long long* __restrict__ acc)
 {
@@ -109,9 +140,9 @@ __device__ __forceinline__ void al_flush(long long (&v)[32], int n_used, int n_g
 
 static bool al_finite(const double* a, int n) { for (int i = 0; i < n; ++i) if (!std::isfinite(a[i])) return false; return true; }
 
-static long long* al_pinned(tsl_tsdf* m) { return reinterpret_cast<long long*>(m->h_ints + 128); }      // the upper part of the pinned scratch: 40 x int64
+static long long* al_pinned(tsl_tsdf* m) { return reinterpret_cast<long long*>(m->h_ints + 128); }      // the upper part of the pinned scratch: room for 192 x int64
 
-// `bytes` (at most 40 x int64) at `dev` to `out` on the host: through the pinned buffer on q; q is idle when it returns
+// `bytes` (at most 192 x int64; the widest reader takes 80) at `dev` to `out` on the host: through the pinned buffer on q; q is idle when it returns
 static int al_read_back(tsl_tsdf* m, hipStream_t q, const void* dev, size_t bytes, void* out)
 {
     TSL_HIP(hipMemcpyAsync(al_pinned(m), dev, bytes, hipMemcpyDeviceToHost, q));
@@ -129,11 +160,10 @@ static void al_system(const tsl_align_sums* s, double damping, double Hm[6][6], 
     for (int a = 0; a < 6; ++a) { b[a] = (double)s->b[a] * (1.0 / 1048576.0); Hm[a][a] += damping * Hm[a][a]; }
 }
 
-// xi = -H^-1 b by Cholesky L L^T without pivoting, column by column; false (xi = 0) when a pivot is <= 0 or not finite
-static bool al_solve(const tsl_align_sums* s, double damping, double xi[6])
+// xi = -H^-1 b of a ready system by Cholesky L L^T without pivoting, column by column; false (xi = 0) when a pivot is <= 0 or not finite
+static bool al_solve_system(const double Hm[6][6], const double b[6], double xi[6])
 {
-    double Hm[6][6], b[6], Lm[6][6], y[6];
-    al_system(s, damping, Hm, b);
+    double Lm[6][6], y[6];
     for (int a = 0; a < 6; ++a) xi[a] = 0.0;
     for (int j = 0; j < 6; ++j) {
         double d = Hm[j][j];
@@ -161,6 +191,29 @@ static bool al_solve(const tsl_align_sums* s, double damping, double xi[6])
     for (int a = 0; a < 6; ++a) xi[a] = x[a];
     return true;
 }
+
+static bool al_solve(const tsl_align_sums* s, double damping, double xi[6])
+{
+    double Hm[6][6], b[6];
+    al_system(s, damping, Hm, b);
+    return al_solve_system(Hm, b, xi);
+}
+
+// the system of the depth-and-colour step: Hd = Hg * 2^-20 + lambda * (Hc * 2^-20), bd likewise, then the damping
+static bool al_solve_rgbd(const tsl_align_rgbd_sums* s, double lambda, double damping, double xi[6])
+{
+    double Hg[6][6], bg[6], Hc[6][6], bc[6];
+    al_system(&s->geo, 0.0, Hg, bg); al_system(&s->col, 0.0, Hc, bc);
+    for (int a = 0; a < 6; ++a) {
+        for (int c = 0; c < 6; ++c) Hg[a][c] = Hg[a][c] + lambda * Hc[a][c];
+        bg[a] = bg[a] + lambda * bc[a];
+    }
+    for (int a = 0; a < 6; ++a) Hg[a][a] += damping * Hg[a][a];
+    return al_solve_system(Hg, bg, xi);
+}
+
+static int64_t al_used(const tsl_align_sums& s) { return s.n_used; }
+static int64_t al_used(const tsl_align_rgbd_sums& s) { return s.geo.n_used; }                 // colour alone does not fix depth
 
 // the Cayley map of omega = xi[3..5]: R <- C R, T <- C T + v
 static void al_retract(const double xi[6], double R[9], double T[3])
@@ -195,9 +248,10 @@ static int track_check(const tsl_track_cfg* t, const char* who)
     return TSL_OK;
 }
 
-// The iteration over the levels of a checked tsl_track_cfg.  lin(stride, R, T, &sums) linearises at the float64 pose (R, T) and returns an error code.
-template <class Lin>
-static int al_iterate(const double R0[9], const double T0[3], const tsl_track_cfg* t, Lin lin, double R_out[9], double T_out[3], tsl_track_report* rep)
+// The iteration over the levels of a checked tsl_track_cfg, for any sums type (al_used gives its count) and its report.  lin(stride, R, T, &sums)
+// linearises at the float64 pose (R, T) and returns an error code; solve(&sums, damping, xi) is the step, false when singular.
+template <class Sums, class Report, class Lin, class Solve>
+static int al_iterate_with(const double R0[9], const double T0[3], const tsl_track_cfg* t, Lin lin, Solve solve, double R_out[9], double T_out[3], Report* rep)
 {
     double R[9], T[3], Rl[9], Tl[3];                               // the current pose; the last one that gave a step
     std::memcpy(R, R0, sizeof(R)); std::memcpy(T, T0, sizeof(T)); std::memcpy(Rl, R0, sizeof(Rl)); std::memcpy(Tl, T0, sizeof(Tl));
@@ -207,10 +261,10 @@ static int al_iterate(const double R0[9], const double T0[3], const tsl_track_cf
     for (int l = 0; l < t->n_levels && !failed; ++l) {
         status = 1;
         for (int k = 0; k < t->iters[l]; ++k) {
-            tsl_align_sums s; double xi[6] = { 0, 0, 0, 0, 0, 0 };
+            Sums s; double xi[6] = { 0, 0, 0, 0, 0, 0 };
             const int rc = lin(t->stride[l], R, T, &s); if (rc) return rc;
-            const bool lost = s.n_used < min_used, singular = !lost && !al_solve(&s, t->damping, xi);
-            if (rep) { tsl_track_iter& it = rep->it[n]; std::memcpy(it.R, R, sizeof(R)); std::memcpy(it.T, T, sizeof(T)); std::memcpy(it.xi, xi, sizeof(xi)); it.sums = s; }
+            const bool lost = al_used(s) < min_used, singular = !lost && !solve(&s, t->damping, xi);
+            if (rep) { auto& it = rep->it[n]; std::memcpy(it.R, R, sizeof(R)); std::memcpy(it.T, T, sizeof(T)); std::memcpy(it.xi, xi, sizeof(xi)); it.sums = s; }
             ++n;
             if (lost || singular) { status = lost ? 2 : 3; failed = true; break; }
             std::memcpy(Rl, R, sizeof(R)); std::memcpy(Tl, T, sizeof(T));
@@ -222,6 +276,13 @@ static int al_iterate(const double R0[9], const double T0[3], const tsl_track_cf
     std::memcpy(R_out, failed ? Rl : R, sizeof(R)); std::memcpy(T_out, failed ? Tl : T, sizeof(T));
     if (rep) { rep->status = status; rep->iterations = n; }
     return TSL_OK;
+}
+
+// the iteration on the 33 integers with the step of tsl_align_solve
+template <class Lin>
+static int al_iterate(const double R0[9], const double T0[3], const tsl_track_cfg* t, Lin lin, double R_out[9], double T_out[3], tsl_track_report* rep)
+{
+    return al_iterate_with<tsl_align_sums>(R0, T0, t, lin, al_solve, R_out, T_out, rep);
 }
 
 }  // namespace tsl

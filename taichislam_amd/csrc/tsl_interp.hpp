@@ -1,5 +1,5 @@
 // tsl_interp.hpp -- the trilinear cell read shared by the ESDF point queries (tsl_esdf_query.hip), the view renderer (tsl_render.hip) and the frame-to-model
-// alignment (tsl_align.hip): the cell of a
+// alignments (tsl_align.hip; tsl_align_rgbd.hip reads the colours of the same corners with tsdf_read_cell_lum): the cell of a
 // coordinate, the pool bricks of its 8 corners, and the interpolant with its gradient in ONE fixed f32 order of evaluation, which is the contract
 // tests/esdf_query_ref.py and tests/render_view_ref.py restate in numpy bit for bit (DESIGN.md sections 4.6 and 4.7).
 #pragma once
@@ -68,6 +68,31 @@ __device__ __forceinline__ bool tsdf_read_cell(const MapDev& M, const int* __res
     bool known = true;
 #pragma unroll
     for (int c = 0; c < 8; ++c) { known = known && P[c] >= 0 && ob[c] > 0; V[c] = h2f((h16)(tw[c] & 0xffffu)); }
+    return known;
+}
+
+// the luminance of a stored colour {r | g << 16, b}: ((77 r + 150 g) + 29 b) / 256 of the three f16 channels converted to f32
+__device__ __forceinline__ float voxel_luminance(uint2 c)
+{
+    const float r = h2f((h16)(c.x & 0xffffu)), g = h2f((h16)(c.x >> 16)), b = h2f((h16)(c.y & 0xffffu));
+    return ((77.0f * r + 150.0f * g) + 29.0f * b) / 256.0f;
+}
+
+// tsdf_read_cell of a textured map (M.col is not null) that also returns the luminances Y of the 8 corners: all 24 gathers -- tw, obs and one 8-byte
+// load of col per corner -- are issued before any is used.  The values of an unknown cell mean nothing.
+__device__ __forceinline__ bool tsdf_read_cell_lum(const MapDev& M, const int* __restrict__ T, int b0, int b1, int b2, float V[8], float Y[8])
+{
+    if (!(in_volume(M, b0, b1, b2) && in_volume(M, b0 + 1, b1 + 1, b2 + 1))) return false;
+    int l000; const int bb = brick_of(M, b0, b1, b2, &l000);
+    const int li = l000 >> 8, lj = (l000 >> 4) & 15, lk = l000 & 15;
+    int P[8]; cell_bricks(M, T, bb, li, lj, lk, P);
+    const uint2* __restrict__ col = reinterpret_cast<const uint2*>(M.col);
+    uint32_t tw[8]; int ob[8]; uint2 cc[8];
+#pragma unroll
+    for (int c = 0; c < 8; ++c) { const size_t v = corner_voxel(P, c, li, lj, lk); tw[c] = M.tw[v]; ob[c] = M.obs[v]; cc[c] = col[v]; }
+    bool known = true;
+#pragma unroll
+    for (int c = 0; c < 8; ++c) { known = known && P[c] >= 0 && ob[c] > 0; V[c] = h2f((h16)(tw[c] & 0xffffu)); Y[c] = voxel_luminance(cc[c]); }
     return known;
 }
 

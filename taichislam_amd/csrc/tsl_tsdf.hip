@@ -1609,7 +1609,7 @@ int tsl_tsdf_prof_enable(tsl_tsdf* m, int on)
 }
 int tsl_tsdf_prof_query(tsl_tsdf* m, int kid, double* total_ms, int64_t* launches)
 {
-    TSL_REQUIRE(m, "null"); TSL_REQUIRE(kid >= 0 && kid < TSL_K_COUNT, "bad kernel id"); TSL_HIP(hipSetDevice(m->device));
+    TSL_REQUIRE(m, "null"); TSL_REQUIRE(kid >= 0 && kid < TSL_K_END, "bad kernel id"); TSL_HIP(hipSetDevice(m->device));
     TSL_HIP(hipStreamSynchronize(ms(m)));
     for (auto& s : m->prof) {
         float ms = 0.0f;

@@ -294,7 +294,7 @@ struct tsl_tsdf {
     EsdfSlot esdf_slot[TSL_ESDF_SLOTS]; int esdf_tail, esdf_npend, esdf_rounds_seen, esdf_round_cap; bool esdf_short; tsl_esdf_totals_t esdf_tot;   // updates in flight (tsl_esdf.hip)
     // profiling
     bool prof_on, prof_open, prof_group; unsigned prof_mask; std::vector<tsl::ProfSlot> prof; std::vector<hipEvent_t> prof_free;
-    double prof_ms[TSL_K_COUNT]; int64_t prof_n[TSL_K_COUNT];
+    double prof_ms[TSL_K_END]; int64_t prof_n[TSL_K_END];
     int semantics;                       // 0: BATCHED (exact per-frame sums applied once), 1: the reference-literal sequential replay (tsl_sequential.hip)
     int seq_impl;                        // 1: per-brick replay runs built on the brick pipeline (default), 0: round 3's two global radix sorts (one frame per batch; kept as a cross-check)
     bool seq_ready; int64_t seq_bytes0;      /* bytes of the literal scratch inside m->bytes: seq_release takes exactly those out of the account again */

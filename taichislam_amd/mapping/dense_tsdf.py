@@ -126,7 +126,43 @@ def align_sums_dict(v):
     return out
 
 
-REGISTER_LEVELS = ((4, 4), (2, 4), (1, 6))       # (stride, iterations) of DenseTSDF.register_submap
+def align_rgbd_config(K=None, shape=(480, 640), stride=1, d_min=None, d_max=None, r_max=None, g_max=None, huber=0.0, rc_max=None, gc_max=None, huber_c=0.0,
+                      counts_only=False):
+    """The tsl_align_rgbd_cfg of DenseTSDF.align_rgbd_linearize / track_rgbd: align_config and the colour gates; None = the default (passed as 0)."""
+    cfg = _lib.AlignRgbdCfg()
+    cfg.a = align_config(K, shape, stride, d_min, d_max, r_max, g_max, huber, counts_only)
+    for name, v in (("rc_max", rc_max), ("gc_max", gc_max), ("huber_c", huber_c)):
+        if v is not None:
+            setattr(cfg, name, float(v))
+    return cfg
+
+
+def align_rgbd_sums_dict(sums):
+    """{"geo", "col"}: the two dicts of align_linearize from a tsl_align_rgbd_sums"""
+    v = np.frombuffer(sums, dtype=np.int64)
+    return {"geo": align_sums_dict(v[:33]), "col": align_sums_dict(v[33:66])}
+
+
+def _rgbd_images(who, depth, rgb, host=False):
+    """(depth pointer, rgb pointer, (h, w), keep-alive, side) of a uint16 [h, w] depth image and the uint8 [h, w, 3] colour image registered to it: two
+    numpy arrays or two torch CUDA tensors.  host: tensors are copied to the host (a host-form call)."""
+    ptr, shape, keep, on_dev = _depth_image(depth)
+    if on_dev != _is_device_tensor(rgb):
+        raise ValueError(f"{who}: depth and rgb must both be numpy arrays or both torch CUDA tensors")
+    if on_dev and not host:
+        if not (rgb.dim() == 3 and rgb.is_contiguous() and rgb.dtype == _torch().uint8 and tuple(rgb.shape) == (shape[0], shape[1], 3) and rgb.device == keep.device):
+            raise ValueError(f"{who}: rgb must be a contiguous uint8 [h, w, 3] tensor on the depth image's device")
+        return ptr, C.c_void_p(rgb.data_ptr()), shape, (keep, rgb), device_side(keep.device)
+    if on_dev:
+        keep, rgb = keep.cpu().numpy().view(np.uint16), rgb.cpu().numpy()
+        ptr = _vp(keep)
+    c = np.ascontiguousarray(np.asarray(rgb, dtype=np.uint8))
+    if c.shape != (shape[0], shape[1], 3):
+        raise ValueError(f"{who}: rgb must be uint8 [h, w, 3] with the depth image's h and w")
+    return ptr, _vp(c), shape, (keep, c), HOST
+
+
+REGISTER_LEVELS = ((4, 4), (2, 4), (1, 6))      # (stride, iterations) of DenseTSDF.register_submap
 
 
 def register_config(stride=1, w_min=0, band=0, r_max=0, g_max=0, huber=0, counts_only=False):
@@ -1478,6 +1514,58 @@ class DenseTSDF(BaseMap):
         side = device_side(keep.device) if on_dev else HOST
         side.call(self.L.tsl_tsdf_track_depth, self.L.tsl_tsdf_track_depth_dev, self.h, r, t, C.byref(cfg), C.byref(tc), ptr, ro, to, C.byref(rep))
         return Ro.reshape(3, 3), To, _track_info(rep)
+
+    # ---- depth-and-colour alignment (tsl_align_rgbd.hip) ------------------------------------------
+    def align_rgbd_linearize(self, depth, rgb, R, T, K=None, stride=1, d_min=None, d_max=None, r_max=None, g_max=None, huber=0.0, rc_max=None, gc_max=None,
+                             huber_c=0.0, device=False, counts_only=False):
+        """The normal equations of aligning a depth image (uint16 millimetres [h, w]) and the colour image registered to it (uint8 [h, w, 3]) to the textured
+        TSDF at the camera-to-map pose (R, T): the geometric term of align_linearize and a colour term, the luminance the map stores at the warped pixel
+        minus the luminance of the image.  Returns {"geo": ..., "col": ...}, each the dict of align_linearize; geo is exactly what align_linearize returns,
+        col has J = (grad Y, p x grad Y) and the residual Y - yi, n_far counting the pixels off the surface (|s| > r_max) or with |Y - yi| > rc_max, n_grad
+        those whose luminance gradient is 0 or longer than gc_max.  None = the default: rc_max 1, gc_max 1 / voxel; huber_c = 0 is off.  Both images are
+        numpy arrays or both torch CUDA tensors; device=True takes tensors and returns an int64 tensor of 80 on the device (geo in [0, 33), col in
+        [40, 73), the rest zeros), asynchronously, ordered with torch.cuda.current_stream (tsl_tsdf_align_rgbd_linearize_dev).  counts_only=True leaves
+        H, b and e of both halves at 0 (the A/B switch of tools/bench_track_rgbd.py)."""
+        ptr, cptr, shape, keep, side = _rgbd_images("align_rgbd_linearize", depth, rgb, host=not device)
+        cfg = align_rgbd_config(K, shape, stride, d_min, d_max, r_max, g_max, huber, rc_max, gc_max, huber_c, counts_only)
+        r, t = _dptr(R, 9)[1], _dptr(T, 3)[1]
+        if device:
+            if side is HOST:
+                raise ValueError("align_rgbd_linearize: device=True takes torch CUDA tensors")
+            out = side.out(80, "i8")
+            side.call(None, self.L.tsl_tsdf_align_rgbd_linearize_dev, self.h, r, t, C.byref(cfg), ptr, cptr, side.ptr(out))
+            return out
+        sums = _lib.AlignRgbdSums()
+        _lib.check(self.L.tsl_tsdf_align_rgbd_linearize(self.h, r, t, C.byref(cfg), ptr, cptr, C.byref(sums)))
+        return align_rgbd_sums_dict(sums)
+
+    def track_rgbd(self, depth, rgb, R, T, K=None, levels=((8, 4), (4, 4), (2, 6)), colour_weight=None, balance=1.0, min_step=1e-4, damping=0.0, min_used=None,
+                   **gates):
+        """track_depth with the colour term of align_rgbd_linearize: every step solves Hg + lambda Hc, so the pose is also held in the directions in which
+        the geometry does not change (along a flat wall, down a corridor) as long as the surface has texture.  colour_weight: lambda >= 0, or None =
+        automatic: balance * trace of the translation block of Hg / that of Hc at the first linearisation, held for the whole call (0 when the view has
+        no texture: pure geometry).  Returns (R 3 x 3, T 3, info) shaped as track_depth's with info["lambda"] the weight that was used and every record
+        holding geo and col, the dicts of align_linearize; the track is lost when the geometric n_used falls below min_used.  depth, rgb: numpy arrays or
+        torch CUDA tensors (ordered with torch.cuda.current_stream); gates: the d_min / d_max / r_max / g_max / huber / rc_max / gc_max / huber_c of
+        align_rgbd_linearize."""
+        ptr, cptr, shape, keep, side = _rgbd_images("track_rgbd", depth, rgb)
+        cfg = align_rgbd_config(K, shape, 1, **gates)
+        tc = _track_config(levels, min_step, damping, min_used)
+        r, t = _dptr(R, 9)[1], _dptr(T, 3)[1]
+        Ro, To, ro, to = _pose_out()
+        rep = _lib.TrackRgbdReport()
+        lam = -1.0 if colour_weight is None else float(colour_weight)
+        if lam < 0.0 and colour_weight is not None:
+            raise ValueError("track_rgbd: colour_weight must not be negative (None = automatic)")
+        side.call(self.L.tsl_tsdf_track_rgbd, self.L.tsl_tsdf_track_rgbd_dev, self.h, r, t, C.byref(cfg), C.byref(tc), lam, float(balance), ptr, cptr, ro, to,
+                  C.byref(rep))
+        records = []
+        for i in range(rep.iterations):
+            it = rep.it[i]
+            rec = align_rgbd_sums_dict(it.sums)
+            rec.update(R=np.array(it.R[:], np.float64).reshape(3, 3), T=np.array(it.T[:], np.float64), xi=np.array(it.xi[:], np.float64))
+            records.append(rec)
+        return Ro.reshape(3, 3), To, {"status": int(rep.status), "iterations": int(rep.iterations), "lambda": float(rep.lam), "records": records}
 
     # ---- scan-to-model alignment (tsl_align_points.hip, DESIGN.md section 4.8.1) -------------------------------------------
     def align_points_linearize(self, xyz, R, T, stride=1, d_min=None, d_max=None, r_max=None, g_max=None, huber=0.0, per_point=False, device=False,
