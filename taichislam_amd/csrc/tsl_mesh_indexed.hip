@@ -1,26 +1,22 @@
 // tsl_mesh_indexed.hip -- the marching-cubes mesh of generate_mesh(1) as an INDEXED mesh: one vertex per grid edge that a valid cell's case names,
 // in ascending edge-key order, and int32 triangles over those rows in ascending cell-key order (include/taichislam_hip.h, "indexed mesh"; DESIGN.md
-// "Indexed marching-cubes mesh").  The soup of tsl_mesh.hip is untouched; the cell rule, the case table and the f16 arithmetic are the same.
+// "Indexed marching-cubes mesh").  The cell, tile and vertex rules are those of tsl_mc.hpp, shared with the soup of tsl_mesh.hip.
 //
 // No atomic decides an output position.  A vertex row is  base_v[brick] + (used edges of the brick below this one)  and a triangle row is
 // base_t[brick] + (triangles of the brick's cells below this one); the bases are an exclusive scan of the per-brick totals in ascending brick-key
 // order (the pool's allocation order plays no part):
-//   k_mi_summary   per brick in use: its key for the sort, and whether it holds a value < 0 / one that is not (the skip test of k_marching_cubes_lds)
+//   k_mi_summary   per brick in use: its key for the sort, and its sign flags
 //   radix sort     the bricks in use by key (rocPRIM); their number is read first -- it sizes the sort and the scan, which otherwise run over the whole pool
 //   k_mi_count     per brick, 19^3 tile in LDS: which of its 3 x 4096 edges are used (a bitmap in key order, with a running count per word),
 //                  and the totals { used edges, triangles }
 //   k_mi_gather, inclusive scan (rocPRIM), k_mi_scatter      totals in key order -> base per pool brick
 //   k_mi_emit      per brick: one lane per used edge writes the vertex row; every triangle corner finds the row of its edge through the bitmap
 //                  of the brick that owns the edge (this brick or one of its seven +1 neighbours)
-#include "tsl_tsdf.hpp"
-#include "mc_tables_data.h"
+#include "tsl_mc.hpp"
 #include <rocprim/rocprim.hpp>
 
 namespace tsl {
 
-#define MI_EPS 1e-6f                                                         // marching_cube_mesher.py:6
-#define MI_T 19                                                              // the tile: brick coordinates -1 .. 17
-#define MI_T3 (MI_T * MI_T * MI_T)
 #define MI_C 17                                                              // cells -1 .. 15 per axis name the edges a brick owns
 #define MI_C3 (MI_C * MI_C * MI_C)
 #define MI_WORDS 384                                                         // 3 x 4096 edge bits per brick; bit l * 3 + axis = the brick's part of the edge key
@@ -44,19 +40,12 @@ struct MeshIdxState {
     bool valid, ready;
 };
 
-__device__ __forceinline__ int mi_tile(int x, int y, int z) { return (x * MI_T + y) * MI_T + z; }      // tile coords = brick coords + 1
 __device__ __forceinline__ int mi_cell(int x, int y, int z) { return (x * MI_C + y) * MI_C + z; }      // cell coords = brick coords + 1
-__device__ __forceinline__ bool mi_bit(const uint32_t* b, int i) { return (b[i >> 5] >> (i & 31)) & 1u; }
-// cube corner q -> offset (grid_xyz :196-206)
-__device__ __forceinline__ void mi_corner(int q, int* d) { d[0] = ((q + 1) >> 1) & 1; d[1] = (q >> 1) & 1; d[2] = (q >> 2) & 1; }
-// table edge e (edges_grid_id :208-221) -> the offset of its LOWER corner and its axis: the grid edge it is, whichever way the table walks it
+// table edge e -> the offset of its LOWER corner and its axis: the grid edge it is, whichever way the table walks it
 __device__ __forceinline__ int mi_edge(int e, int* d)
 {
-    int a, b;
-    if (e < 4) { a = e; b = (e + 1) & 3; }
-    else if (e < 8) { a = e; b = 4 + ((e - 3) & 3); }
-    else { a = e - 8; b = e - 4; }
-    int da[3], db[3]; mi_corner(a, da); mi_corner(b, db);
+    int a, b; mc_edge_corners(e, &a, &b);
+    int da[3], db[3]; mc_corner(a, da); mc_corner(b, db);
     int axis = 0;
     for (int c = 0; c < 3; ++c) { d[c] = da[c] < db[c] ? da[c] : db[c]; if (da[c] != db[c]) axis = c; }
     return axis;
@@ -65,130 +54,33 @@ __device__ __forceinline__ int mi_edge(int e, int* d)
 __global__ void __launch_bounds__(256) k_mi_summary(MapDev M, MiDev D, int nused)
 {
     for (int p = blockIdx.x; p < nused; p += gridDim.x) {
-        const uint4* tw = reinterpret_cast<const uint4*>(M.tw + (size_t)p * TSL_BRK3);
-        uint32_t f = 0u;
-#pragma unroll
-        for (int q = 0; q < TSL_BRK3 / 4 / 256; ++q) {
-            const uint4 v = tw[q * 256 + threadIdx.x];
-            const uint32_t w4[4] = { v.x, v.y, v.z, v.w };
-#pragma unroll
-            for (int u = 0; u < 4; ++u) f |= h2f((h16)(w4[u] & 0xffffu)) < 0.0f ? 1u : 2u;
-        }
-        const int neg = __syncthreads_or((int)(f & 1u)), nn = __syncthreads_or((int)(f & 2u));
-        if (threadIdx.x == 0) { D.flags[p] = (neg ? 1u : 0u) | (nn ? 2u : 0u); D.key[p] = (uint32_t)M.owner[p]; D.ord[p] = p; D.cnt[p] = 0ull; }
+        const uint32_t f = mc_brick_flags(M, p);
+        if (threadIdx.x == 0) { D.flags[p] = f; D.key[p] = (uint32_t)M.owner[p]; D.ord[p] = p; D.cnt[p] = 0ull; }
     }
-}
-
-// The brick's neighbourhood: the pool indices of the 27 bricks around it, and -- unless every corner of every cell that can name one of the brick's
-// edges lies on one side of zero (then *skip) -- the 19^3 tile of f16 TSDF bits and observed bits.  Ends with the tile visible to every thread.
-__device__ __forceinline__ void mi_gather(const MapDev& M, const MiDev& D, int nused, int p, int s, int bi, int bj, int bk,
-                                          int* s_nb, uint16_t* s_t, uint32_t* s_o, int* s_skip)
-{
-    __syncthreads();                                                     // the previous brick's tile is no longer read
-    if (threadIdx.x < 64) {
-        int np = -1; bool corner = false;
-        if (threadIdx.x < 27) {
-            const int di = (int)threadIdx.x / 9 - 1, dj = ((int)threadIdx.x / 3) % 3 - 1, dk = (int)threadIdx.x % 3 - 1;
-            const int i = bi + di, j = bj + dj, k = bk + dk;
-            np = (i < 0 || i >= M.nbx || j < 0 || j >= M.nbx || k < 0 || k >= M.nbz) ? -1 : pool_lookup_ro(M, s, (i * M.nbx + j) * M.nbz + k);
-            if (np >= nused) np = -1;                                       // (never: the table only names bricks in use)
-            s_nb[threadIdx.x] = np;
-            corner = di >= 0 && dj >= 0 && dk >= 0;                         // a used edge of this brick has its corners in these eight, on two sides of zero
-        }
-        const uint32_t f = corner ? (np >= 0 ? D.flags[np] : 2u) : 0u;      // (no brick: the corners read 0)
-        const bool neg = __ballot((f & 1u) != 0u) != 0ull, nn = __ballot((f & 2u) != 0u) != 0ull;
-        if (threadIdx.x == 0) *s_skip = (neg && nn) ? 0 : 1;
-    }
-    for (int i = threadIdx.x; i < (MI_T3 + 31) / 32; i += 256) s_o[i] = 0u;
-    __syncthreads();
-    if (*s_skip) return;                                                 // (uniform)
-    for (int c = 0; c < MI_T3; c += 4 * 256) {                           // four independent loads per thread and round
-        uint32_t tw[4]; int8_t ob[4]; bool ok[4]; int tt[4];
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-            const int t = c + u * 256 + (int)threadIdx.x;
-            tt[u] = t;
-            const int tc = t < MI_T3 ? t : 0;
-            const int tz = tc % MI_T, ty = (tc / MI_T) % MI_T, tx = tc / (MI_T * MI_T);
-            const int np = s_nb[(((tx + 15) >> 4) * 3 + ((ty + 15) >> 4)) * 3 + ((tz + 15) >> 4)];
-            ok[u] = t < MI_T3 && np >= 0 && in_volume(M, bi * 16 + tx - 1 - M.hN, bj * 16 + ty - 1 - M.hN, bk * 16 + tz - 1 - M.hNz);
-            const size_t v = (size_t)(ok[u] ? np : p) * TSL_BRK3 + ((((tx + 15) & 15) << 8) | (((ty + 15) & 15) << 4) | ((tz + 15) & 15));
-            tw[u] = M.tw[v]; ob[u] = M.obs[v];
-        }
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-            const int t = tt[u];
-            if (t >= MI_T3) continue;
-            s_t[t] = ok[u] ? (uint16_t)(tw[u] & 0xffffu) : (uint16_t)0;
-            if (ok[u] && ob[u] > 0) atomicOr(&s_o[t >> 5], 1u << (t & 31));
-        }
-    }
-    __syncthreads();
-}
-
-// is the cell at brick coordinates (x, y, z), each -1 .. 15, valid: its own voxel observed and below the threshold (:184), all eight corners observed (:133-138)
-__device__ __forceinline__ bool mi_valid(const uint16_t* s_t, const uint32_t* s_o, int x, int y, int z, float thres)
-{
-    const int t0 = mi_tile(x + 1, y + 1, z + 1);
-    if (!(mi_bit(s_o, t0) && h2f(s_t[t0]) < thres)) return false;
-    for (int q = 1; q < 8; ++q) {
-        int d[3]; mi_corner(q, d);
-        if (!mi_bit(s_o, mi_tile(x + 1 + d[0], y + 1 + d[1], z + 1 + d[2]))) return false;
-    }
-    return true;
-}
-// the case of the cell (:141-144)
-__device__ __forceinline__ int mi_case(const uint16_t* s_t, int x, int y, int z)
-{
-    int c = 0;
-    for (int q = 0; q < 8; ++q) {
-        int d[3]; mi_corner(q, d);
-        if (h2f(s_t[mi_tile(x + 1 + d[0], y + 1 + d[1], z + 1 + d[2])]) < 0.0f) c |= 1 << q;
-    }
-    return c;
-}
-__device__ __forceinline__ int mi_ntri(unsigned long long tri)
-{
-    int n = 0;
-    for (int t = 0; t < 5; ++t) if (((tri >> (12 * t)) & 0xfull) != 0xfull) ++n;                      // :173-177 (triTable[cube][3t] != -1)
-    return n;
-}
-// exclusive scan of one value per thread over the block's 256 threads (s_w: 5 ints); *total = the block's sum
-__device__ __forceinline__ int mi_block_scan(int mine, int* s_w, int* total)
-{
-    int incl = mine;
-    for (int d = 1; d < 64; d <<= 1) { const int o = __shfl_up(incl, d); if (lane_id() >= d) incl += o; }
-    __syncthreads();
-    if (lane_id() == 63) s_w[threadIdx.x >> 6] = incl;
-    __syncthreads();
-    int first = incl - mine;
-    for (int w = 0; w < (int)(threadIdx.x >> 6); ++w) first += s_w[w];
-    *total = s_w[0] + s_w[1] + s_w[2] + s_w[3];
-    return first;
 }
 
 // Thread t owns the 16 voxels l = 16 t .. 16 t + 15 of the brick (one z-run): consecutive threads, consecutive keys.
 __global__ void __launch_bounds__(256) k_mi_count(MapDev M, MiDev D, float thres, int nused)
 {
     __shared__ unsigned long long s_tri[256];
-    __shared__ uint16_t s_t[MI_T3];
-    __shared__ uint32_t s_o[(MI_T3 + 31) / 32];
+    __shared__ uint16_t s_t[MC_T3];
+    __shared__ uint32_t s_o[MC_OWORDS];
     __shared__ uint32_t s_cv[(MI_C3 + 31) / 32];          // valid cells, cell coordinates -1 .. 15
     __shared__ uint32_t s_bits[MI_WORDS];
-    __shared__ int s_nb[27], s_w[5], s_skip;
+    __shared__ int s_nb[27], s_w[4], s_skip;
     s_tri[threadIdx.x] = MC_TRI_PACKED[threadIdx.x];
     for (int p = blockIdx.x; p < nused; p += gridDim.x) {
         const int owner = M.owner[p];
         const int s = owner / M.nb3, b = owner - s * M.nb3;
         const int bk = b % M.nbz, bj = (b / M.nbz) % M.nbx, bi = b / (M.nbz * M.nbx);
-        mi_gather(M, D, nused, p, s, bi, bj, bk, s_nb, s_t, s_o, &s_skip);
+        mc_gather(M, D.flags, nused, p, s, bi, bj, bk, 0, MC_T3, s_nb, s_t, s_o, &s_skip);
         if (s_skip) continue;                                            // (uniform) cnt[p] stays 0: no edge of this brick is used, no cell of it has a triangle
         for (int i = threadIdx.x; i < (MI_C3 + 31) / 32; i += 256) s_cv[i] = 0u;
         for (int i = threadIdx.x; i < MI_WORDS; i += 256) s_bits[i] = 0u;
         __syncthreads();
         for (int c = threadIdx.x; c < MI_C3; c += 256) {
             const int z = c % MI_C, y = (c / MI_C) % MI_C, x = c / (MI_C * MI_C);
-            if (mi_valid(s_t, s_o, x - 1, y - 1, z - 1, thres)) atomicOr(&s_cv[c >> 5], 1u << (c & 31));
+            if (mc_valid(s_t, s_o, x - 1, y - 1, z - 1, thres)) atomicOr(&s_cv[c >> 5], 1u << (c & 31));
         }
         __syncthreads();
         // an edge is used when a valid cell among the four around it names it; a case names exactly the edges whose corners differ in sign
@@ -196,17 +88,17 @@ __global__ void __launch_bounds__(256) k_mi_count(MapDev M, MiDev D, float thres
         unsigned long long mybits = 0ull;                                // 48 bits: 16 voxels x 3 axes
         int mytri = 0;
         for (int lz = 0; lz < 16; ++lz) {
-            const bool n0 = h2f(s_t[mi_tile(lx + 1, ly + 1, lz + 1)]) < 0.0f;
+            const bool n0 = h2f(s_t[mc_tile(lx + 1, ly + 1, lz + 1)]) < 0.0f;
             const int cx = lx + 1, cy = ly + 1, cz = lz + 1;             // cell coordinates of the voxel's own cell
-            const bool v000 = mi_bit(s_cv, mi_cell(cx, cy, cz)), v100 = mi_bit(s_cv, mi_cell(cx - 1, cy, cz)), v010 = mi_bit(s_cv, mi_cell(cx, cy - 1, cz)),
-                       v001 = mi_bit(s_cv, mi_cell(cx, cy, cz - 1)), v110 = mi_bit(s_cv, mi_cell(cx - 1, cy - 1, cz)), v101 = mi_bit(s_cv, mi_cell(cx - 1, cy, cz - 1)),
-                       v011 = mi_bit(s_cv, mi_cell(cx, cy - 1, cz - 1));
-            const bool nx = h2f(s_t[mi_tile(lx + 2, ly + 1, lz + 1)]) < 0.0f, ny = h2f(s_t[mi_tile(lx + 1, ly + 2, lz + 1)]) < 0.0f,
-                       nz = h2f(s_t[mi_tile(lx + 1, ly + 1, lz + 2)]) < 0.0f;
+            const bool v000 = mc_bit(s_cv, mi_cell(cx, cy, cz)), v100 = mc_bit(s_cv, mi_cell(cx - 1, cy, cz)), v010 = mc_bit(s_cv, mi_cell(cx, cy - 1, cz)),
+                       v001 = mc_bit(s_cv, mi_cell(cx, cy, cz - 1)), v110 = mc_bit(s_cv, mi_cell(cx - 1, cy - 1, cz)), v101 = mc_bit(s_cv, mi_cell(cx - 1, cy, cz - 1)),
+                       v011 = mc_bit(s_cv, mi_cell(cx, cy - 1, cz - 1));
+            const bool nx = h2f(s_t[mc_tile(lx + 2, ly + 1, lz + 1)]) < 0.0f, ny = h2f(s_t[mc_tile(lx + 1, ly + 2, lz + 1)]) < 0.0f,
+                       nz = h2f(s_t[mc_tile(lx + 1, ly + 1, lz + 2)]) < 0.0f;
             if (n0 != nx && (v000 || v010 || v001 || v011)) mybits |= 1ull << (3 * lz);
             if (n0 != ny && (v000 || v100 || v001 || v101)) mybits |= 1ull << (3 * lz + 1);
             if (n0 != nz && (v000 || v100 || v010 || v110)) mybits |= 1ull << (3 * lz + 2);
-            if (v000) mytri += mi_ntri(s_tri[mi_case(s_t, lx, ly, lz)]);
+            if (v000) mytri += mc_ntri(s_tri[mc_case(s_t, lx, ly, lz)]);
         }
         {   // bit 48 t of the brick's bitmap onwards: word 3 t / 2, at bit 0 (t even) or 16 (t odd)
             const int w = ((int)threadIdx.x * 48) >> 5, sh = ((int)threadIdx.x * 48) & 31;
@@ -218,13 +110,13 @@ __global__ void __launch_bounds__(256) k_mi_count(MapDev M, MiDev D, float thres
         // running count per word: thread t < 192 takes words 2 t, 2 t + 1
         const uint32_t w0 = threadIdx.x < MI_WORDS / 2 ? s_bits[2 * threadIdx.x] : 0u, w1 = threadIdx.x < MI_WORDS / 2 ? s_bits[2 * threadIdx.x + 1] : 0u;
         int nv = 0, nt = 0;
-        const int first = mi_block_scan(__popc(w0) + __popc(w1), s_w, &nv);
+        const int first = mc_block_scan(__popc(w0) + __popc(w1), s_w, &nv);
         if (threadIdx.x < MI_WORDS / 2) {
             const size_t o = (size_t)p * MI_WORDS + 2 * threadIdx.x;
             D.bits[o] = w0; D.bits[o + 1] = w1;
             D.pref[o] = (uint16_t)first; D.pref[o + 1] = (uint16_t)(first + __popc(w0));
         }
-        (void)mi_block_scan(mytri, s_w, &nt);
+        (void)mc_block_scan(mytri, s_w, &nt);
         if (threadIdx.x == 0) D.cnt[p] = (unsigned long long)(uint32_t)nv | (unsigned long long)(uint32_t)nt << 32;
     }
 }
@@ -243,11 +135,11 @@ __global__ void __launch_bounds__(256) k_mi_scatter(MiDev D, int n)
 __global__ void __launch_bounds__(256) k_mi_emit(MapDev M, MiDev D, float thres, float vs, long long max_v, long long max_t, int nused)
 {
     __shared__ unsigned long long s_tri[256];
-    __shared__ uint16_t s_t[MI_T3];
-    __shared__ uint32_t s_o[(MI_T3 + 31) / 32];
+    __shared__ uint16_t s_t[MC_T3];
+    __shared__ uint32_t s_o[MC_OWORDS];
     __shared__ uint32_t s_bits[MI_WORDS];
     __shared__ uint16_t s_list[3 * TSL_BRK3];             // the brick's used edges (bit numbers) in key order
-    __shared__ int s_nb[27], s_w[5], s_skip;
+    __shared__ int s_nb[27], s_w[4], s_skip;
     __shared__ uint32_t s_basev[8];
     s_tri[threadIdx.x] = MC_TRI_PACKED[threadIdx.x];
     for (int p = blockIdx.x; p < nused; p += gridDim.x) {
@@ -256,7 +148,7 @@ __global__ void __launch_bounds__(256) k_mi_emit(MapDev M, MiDev D, float thres,
         const int owner = M.owner[p];
         const int s = owner / M.nb3, b = owner - s * M.nb3;
         const int bk = b % M.nbz, bj = (b / M.nbz) % M.nbx, bi = b / (M.nbz * M.nbx);
-        mi_gather(M, D, nused, p, s, bi, bj, bk, s_nb, s_t, s_o, &s_skip);
+        mc_gather(M, D.flags, nused, p, s, bi, bj, bk, 0, MC_T3, s_nb, s_t, s_o, &s_skip);
         if (s_skip) continue;                                            // (never with a count: the same test as in k_mi_count)
         const int nv = (int)(uint32_t)cnt, nt = (int)(cnt >> 32);
         const unsigned long long base = D.base[p];
@@ -282,35 +174,21 @@ __global__ void __launch_bounds__(256) k_mi_emit(MapDev M, MiDev D, float thres,
             const int lx = l >> 8, ly = (l >> 4) & 15, lz = l & 15;
             const int i = bi * 16 + lx - M.hN, j = bj * 16 + ly - M.hN, k = bk * 16 + lz - M.hNz;
             const int ux = lx + (a == 0), uy = ly + (a == 1), uz = lz + (a == 2);            // the upper corner, brick coordinates 0 .. 16
-            const float v0 = h2f(s_t[mi_tile(lx + 1, ly + 1, lz + 1)]), v1 = h2f(s_t[mi_tile(ux + 1, uy + 1, uz + 1)]);
             const float p0[3] = { (float)i, (float)j, (float)k };
             const float p1[3] = { (float)(i + (a == 0)), (float)(j + (a == 1)), (float)(k + (a == 2)) };
-            float pv[3], mu = 0.0f;
-            if (fabsf(0.0f - v0) < MI_EPS) { pv[0] = p0[0]; pv[1] = p0[1]; pv[2] = p0[2]; }            // vertexInterp :44-60, p0 the lower corner
-            else if (fabsf(0.0f - v1) < MI_EPS) { pv[0] = p1[0]; pv[1] = p1[1]; pv[2] = p1[2]; }
-            else { mu = (0.0f - v0) / h2f(hsub(f2h(v1), f2h(v0))); for (int c = 0; c < 3; ++c) pv[c] = p0[c] + mu * (p1[c] - p0[c]); }      // (valp2 - valp1 of two f16 values is an f16 operation)
-            if (D.c) {                                                   // vertexInterp_color :62-82, the same p0 / p1 and mu
-                const int npu = s_nb[(((ux >> 4) + 1) * 3 + ((uy >> 4) + 1)) * 3 + ((uz >> 4) + 1)];
-                const uint2 ca2 = reinterpret_cast<const uint2*>(M.col)[(size_t)p * TSL_BRK3 + l];
-                const uint2 cb2 = npu >= 0 ? reinterpret_cast<const uint2*>(M.col)[(size_t)npu * TSL_BRK3 + (((ux & 15) << 8) | ((uy & 15) << 4) | (uz & 15))] : make_uint2(0u, 0u);
-                const h16 c0[3] = { (h16)(ca2.x & 0xffffu), (h16)(ca2.x >> 16), (h16)(ca2.y & 0xffffu) };
-                const h16 c1[3] = { (h16)(cb2.x & 0xffffu), (h16)(cb2.x >> 16), (h16)(cb2.y & 0xffffu) };
-                float vc[3] = { h2f(c0[0]), h2f(c0[1]), h2f(c0[2]) };
-                if (h2f(c0[0]) == 0.0f) { for (int c = 0; c < 3; ++c) vc[c] = h2f(c1[c]); }
-                else if (!(h2f(c1[0]) == 0.0f)) { for (int c = 0; c < 3; ++c) vc[c] = h2f(f2h(h2f(c0[c]) + mu * h2f(hsub(c1[c], c0[c])))); }
-                for (int c = 0; c < 3; ++c) D.c[(size_t)row * 3 + c] = vc[c];
-            }
-            // generate_normal :84-93 around the voxel nearest to the vertex: one of the edge's two corners, tile coordinates 1 .. 17
-            // (clamped to that range: a NaN map value makes a NaN vertex, whose nearest voxel is anything)
-            const int q0 = min(max((int)rnd_f(pv[0]) - i + lx + 1, 1), 17), q1 = min(max((int)rnd_f(pv[1]) - j + ly + 1, 1), 17), q2 = min(max((int)rnd_f(pv[2]) - k + lz + 1, 1), 17);
-            const h16 n0 = hsub(s_t[mi_tile(q0 + 1, q1, q2)], s_t[mi_tile(q0 - 1, q1, q2)]);
-            const h16 n1 = hsub(s_t[mi_tile(q0, q1 + 1, q2)], s_t[mi_tile(q0, q1 - 1, q2)]);
-            const h16 n2 = hsub(s_t[mi_tile(q0, q1, q2 + 1)], s_t[mi_tile(q0, q1, q2 - 1)]);
-            const h16 nrm = hsqrt(hadd(hadd(hmul(n0, n0), hmul(n1, n1)), hmul(n2, n2)));
-            const h16 inv = f2h(1.0f / h2f(nrm));
+            float pv[3], mu, nn[3];
+            mc_vertex(h2f(s_t[mc_tile(lx + 1, ly + 1, lz + 1)]), h2f(s_t[mc_tile(ux + 1, uy + 1, uz + 1)]), p0, p1, pv, &mu);      // from the lower corner to the upper one
             const size_t o = (size_t)row * 3;
+            if (D.c) {                                                   // the same corners and mu
+                const int npu = s_nb[(((ux >> 4) + 1) * 3 + ((uy >> 4) + 1)) * 3 + ((uz >> 4) + 1)];
+                const uint2* col = reinterpret_cast<const uint2*>(M.col);
+                float vc[3];
+                mc_colour(col[(size_t)p * TSL_BRK3 + l], npu >= 0 ? col[(size_t)npu * TSL_BRK3 + (((ux & 15) << 8) | ((uy & 15) << 4) | (uz & 15))] : make_uint2(0u, 0u), mu, vc);
+                for (int c = 0; c < 3; ++c) D.c[o + c] = vc[c];
+            }
+            mc_tile_normal(s_t, (int)rnd_f(pv[0]) - i + lx + 1, (int)rnd_f(pv[1]) - j + ly + 1, (int)rnd_f(pv[2]) - k + lz + 1, nn);
             D.v[o] = pv[0] * vs; D.v[o + 1] = pv[1] * vs; D.v[o + 2] = pv[2] * vs;
-            D.n[o] = h2f(hmul(inv, n0)); D.n[o + 1] = h2f(hmul(inv, n1)); D.n[o + 2] = h2f(hmul(inv, n2));
+            D.n[o] = nn[0]; D.n[o + 1] = nn[1]; D.n[o + 2] = nn[2];
             reinterpret_cast<short4*>(D.e)[row] = make_short4((short)i, (short)j, (short)k, (short)a);
         }
         // ---- triangles: thread t walks the cells of its z-run in key order ----
@@ -319,12 +197,12 @@ __global__ void __launch_bounds__(256) k_mi_emit(MapDev M, MiDev D, float thres,
         int mytri = 0;
         uint32_t vmask = 0u;
         for (int lz = 0; lz < 16; ++lz)
-            if (mi_valid(s_t, s_o, lx, ly, lz, thres)) { vmask |= 1u << lz; mytri += mi_ntri(s_tri[mi_case(s_t, lx, ly, lz)]); }
+            if (mc_valid(s_t, s_o, lx, ly, lz, thres)) { vmask |= 1u << lz; mytri += mc_ntri(s_tri[mc_case(s_t, lx, ly, lz)]); }
         int total = 0;
-        long long at = (long long)(base >> 32) + mi_block_scan(mytri, s_w, &total);
+        long long at = (long long)(base >> 32) + mc_block_scan(mytri, s_w, &total);
         for (int lz = 0; lz < 16 && mytri; ++lz) {
             if (!((vmask >> lz) & 1u)) continue;
-            const unsigned long long tri = s_tri[mi_case(s_t, lx, ly, lz)];
+            const unsigned long long tri = s_tri[mc_case(s_t, lx, ly, lz)];
             for (int u = 0; u < 5; ++u) {
                 if (((tri >> (12 * u)) & 0xfull) == 0xfull) continue;
                 if (at < max_t) {

@@ -1,7 +1,8 @@
 """The indexed marching-cubes mesh on the GPU (tsl_mesh_indexed.hip): counts, vertices, normals, colours, edge records and triangles equal the numpy
 restatement (tests/mesh_indexed_ref.py) over the oracle's export bit for bit and row for row, nothing sorted -- on the hand-built scenes of
 tests/mesh_indexed_scenes.py on three geometries and on integrated streams -- plus the relation to the soup, load-order independence, capacities,
-ordering behind queued frames, the device form, an empty map, the refusals, and the soup path left as it was."""
+ordering behind queued frames, the device form, an empty map, the refusals, the soup path left as it was, and NaN map values under the soup's tile
+kernel, which shares the indexed mesh's tile normal."""
 import ctypes as C
 
 import numpy as np
@@ -259,3 +260,44 @@ def test_soup_path_is_untouched_by_an_indexed_call(hip_lib):
     m.generate_indexed_mesh()                                                # ... and the soup's device view still counts the soup's rows
     assert tuple(m.mesh_vertices.to_torch().shape) == (3 * on, 3)
     assert ref._same(m.mesh_vertices.to_torch().cpu().numpy(), v)
+
+
+def _soup_rows(m):
+    """the soup of the last generate_mesh as uint32 rows [positions 9 | normals 9], sorted: the order of the rows is the arrival order of the bricks"""
+    v, nr, _ = m.get_mesh()
+    rows = np.ascontiguousarray(np.concatenate([v.reshape(-1, 9), nr.reshape(-1, 9)], axis=1), np.float32).view(np.uint32)
+    return rows[np.lexsort(rows.T[::-1])]
+
+
+def test_nan_map_values_keep_the_soup_normal_inside_its_tile(hip_lib):
+    """A NaN map value (load_numpy stores what it is given) makes a NaN vertex, whose nearest voxel is anything: the tile kernel clamps the voxel of
+    the normal to its tile, as the indexed mesh does (tsl_mc.hpp, mc_tile_normal).  A flat surface between z = -1 and z = 0 across eight bricks, every
+    voxel observed, NaN in the voxel at brick-local (0, 0, 0) above it and in the one at brick-local (15, 7, 15) below it.  The tile kernel gives
+    the same rows twice (compared as sorted rows of bits: bricks reserve their rows by an atomic, so the order of the rows is not defined) and as
+    many triangles as the indexed mesh; where a triangle's positions are finite it is the gather kernel's triangle, normals included."""
+    idx = ms.box((-10, -10, -4), (9, 9, 3))
+    val = ((idx[:, 2] + 0.5) * 0.04).astype(np.float16)
+    for nan_voxel in ((0, 0, 0), (-1, 7, -1)):
+        val[(idx == np.array(nan_voxel)).all(1)] = np.nan
+    assert np.isnan(val).sum() == 2
+    sc = ms.placed(ms.scene(idx, val, 1.0), "SMALL")
+    g = _map("SMALL", hip_lib)
+    g.load_numpy(0, sc["indices"], sc["TSDF"], sc["W_TSDF"], sc["occupy"], None)
+    m, got = _indexed(g, sc["thres"])
+    tile = []
+    for _ in range(2):
+        m.generate_mesh(1)
+        assert m.num_facelets[None] == got["num_triangles"] > 0
+        tile.append(_soup_rows(m))
+    assert tile[0].tobytes() == tile[1].tobytes(), "two meshes of one map by the tile kernel differ"
+    g.set_option("mesh_gather", 1)
+    try:
+        m.generate_mesh(1)
+        gather = _soup_rows(m)
+    finally:
+        g.set_option("mesh_gather", 0)
+    a, b = (r[np.isfinite(r[:, :9].view(np.float32)).all(1)].view(np.float32) for r in (tile[0], gather))
+    assert 0 < a.shape[0] < tile[0].shape[0], "the map has no NaN vertex, or nothing else"
+    assert a.shape == b.shape and np.array_equal(a[:, :9], b[:, :9]), "the triangles with finite positions differ between the tile and the gather kernel"
+    assert np.array_equal(np.isnan(a[:, 9:]), np.isnan(b[:, 9:])), "a normal is NaN in one kernel only"
+    assert np.isnan(a[:, 9:]).any() and np.array_equal(np.nan_to_num(a[:, 9:]), np.nan_to_num(b[:, 9:])), "normals differ"
