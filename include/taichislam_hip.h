@@ -72,7 +72,7 @@ enum { TSL_K_VOXELIZE = 0, TSL_K_SORT = 1, TSL_K_RAYS = 2, TSL_K_INTEGRATE = 3, 
        TSL_K_NAV_TERRAIN_COLUMNS = 28, TSL_K_NAV_TERRAIN_WINDOW = 29,
        TSL_K_COUNT };
 /* the ids added since: the first enum ends where it always did, prof_query takes every id below TSL_K_END */
-enum { TSL_K_ALIGN_RGBD = 30, TSL_K_END = 31 };
+enum { TSL_K_ALIGN_RGBD = 30, TSL_K_EVICT = 31 /* tsl_tsdf_evict: the pack launch, and the compaction's four launches */, TSL_K_END = 32 };
 
 const char* tsl_version(void);
 const char* tsl_last_error(void);
@@ -146,6 +146,70 @@ int  tsl_tsdf_export_sparse(tsl_tsdf* m, int16_t* idx, uint16_t* tsdf_h, uint16_
 int  tsl_tsdf_import_sparse(tsl_tsdf* m, int sid, const int16_t* idx, const uint16_t* tsdf_h,
                             const uint16_t* w_h, const int8_t* occ, const uint16_t* color_h, int64_t n);   /* load_numpy :442-454 */
 int  tsl_tsdf_export_occupied(tsl_tsdf* m, int16_t* idx, int8_t* occ, int64_t cap, int64_t* n);
+
+/* ---- evict and restore bricks: bounded pool memory for long missions (no counterpart in the reference, whose map is a dense field) -----------
+ * The brick pool hands out 16^3 bricks and, until these calls, only tsl_tsdf_reset gave any back.  tsl_tsdf_evict selects bricks, copies their raw
+ * planes out (the PAYLOAD) and, with release = 1, gives their pool slots back; tsl_tsdf_restore_bricks puts payload rows into a map of the same
+ * geometry.  A payload is lossless: what an evict + restore round trip leaves is, brick for brick, the bytes that were there.
+ *   Brick key: key = s * nb3 + b, s the submap slot (0 on a global map), b = (bi * nbx + bj) * nbz + bk, nbx = ceil(N / 16), nbz = ceil(Nz / 16),
+ *     nb3 = nbx * nbx * nbz.  Brick (bi, bj, bk) holds the voxels 16 * bi - N / 2 .. 16 * bi + 15 - N / 2 of the map-centred index i of
+ *     tsl_tsdf_export_sparse (j alike, k with Nz / 2); where N is no multiple of 16 the last bricks reach past the volume.  The voxel with local
+ *     offsets (li, lj, lk) is element (li << 8) | (lj << 4) | lk of a plane row.
+ *   Selection (tsl_evict_cfg.rule), all integer, evaluated on the device over the bricks in use:
+ *     TSL_EVICT_KEEP_BOX   every brick of the chosen slots whose voxel range does NOT intersect the inclusive voxel box lo <= (i, j, k) <= hi
+ *     TSL_EVICT_CLEAR_BOX  every brick of the chosen slots whose voxel range lies wholly inside the box
+ *                          (a brick the box cuts through stays under both rules; lo > hi on an axis is an argument error)
+ *     TSL_EVICT_KEYS       the bricks named by keys_in[0 .. nkeys): a key listed twice counts once, a key whose brick is absent counts (once) in
+ *                          stats.missing, a key outside [0, max_submap_num * nb3) is an argument error and nothing changes
+ *     sid (box rules): a submap slot, or -1 = every slot; on a global map 0 and -1 mean the same.  The keys rule does not read it.
+ *   Payload: one row per selected brick in ASCENDING KEY order, whatever order the pool holds them in: keys int32 [n], tw uint32 [n][4096] (lo16 the
+ *     TSDF f16 bits, hi16 the weight f16 bits), obs int8 [n][4096], occ int8 [n][4096], col uint16 [n][4096][4] (f16 r, g, b and the pad lane;
+ *     textured maps only, ignored otherwise).  Two maps with the same content give the same bytes.  A null plane is not written.  All planes null
+ *     and release = 0: the call only counts.  All planes null and release = 1: the selection is discarded without a copy (clearing a region).
+ *     cap = rows the buffers hold; cap < stats.selected with any plane given: TSL_ERR_CAPACITY, stats.selected is set, nothing changes.
+ *   Release (release = 1): with top bricks in use and E selected, new_top = top - E; the HOLES (selected pool indices < new_top, ascending) are
+ *     filled by the MOVERS (kept pool indices >= new_top, ascending), mover k into hole k, so the pool stays dense and its order after the call is a
+ *     function of its order before and the selection alone.  Every evicted key leaves the brick table, every slot in [new_top, top) is zero again,
+ *     tsl_tsdf_bricks_in_use gives new_top.  With E > 0 the ESDF is invalidated exactly as tsl_tsdf_reset and tsl_tsdf_import_sparse do (the next
+ *     update is a full one; tsl_esdf_query_points refuses until then); with E = 0 nothing is touched.  release = 0 is a snapshot: the map is untouched.
+ *   Before anything else the queued frames are issued and waited for (tsl_tsdf_sync) and a running ESDF update is finished; a capacity error of
+ *     those frames is returned AFTER the call has done its work, as tsl_tsdf_reset returns it.  Between tsl_tsdf_merge_begin and the merge's finish the
+ *     calls are refused (TSL_ERR_ARG): the merge's sums and its union list name pool bricks.  They work under semantics 0 and 1.
+ *   stats: selected, missing, moved (movers), bricks_before, bricks_after; restore: restored, skipped.
+ * tsl_tsdf_restore_bricks: rows keys[0 .. n) with their planes (tw, obs, occ required; col read on textured maps when given) go back in.  sid = -1:
+ *   every row goes to its own key; sid >= 0: to brick key % nb3 of that slot.  The keys (of the slot they go to) must ascend strictly and lie in
+ *   range, else TSL_ERR_ARG.  A row whose brick exists is a CONFLICT: on_conflict TSL_RESTORE_SKIP drops the row (stats.skipped),
+ *   TSL_RESTORE_OVERWRITE replaces the brick's planes.  All or nothing: the absent bricks are counted first, and when they do not fit max_bricks
+ *   the call returns TSL_ERR_CAPACITY and the map is unchanged.  New bricks are claimed as integration claims them, so their pool order is not
+ *   defined; the content by key is.  The ESDF is invalidated as by tsl_tsdf_import_sparse when a row went in.
+ * tsl_tsdf_brick_keys: the keys of the bricks in use in pool order, *n = their number (keys NULL: only the number; cap < *n: TSL_ERR_CAPACITY).
+ * The _dev forms take device pointers (payload planes 16-byte aligned), run on the handle's stream behind what user_stream has queued, and make
+ * user_stream wait for them; they still wait for the selection's counts, which the host needs for stats and the capacity check. */
+#define TSL_EVICT_KEEP_BOX     0
+#define TSL_EVICT_CLEAR_BOX    1
+#define TSL_EVICT_KEYS         2
+#define TSL_RESTORE_SKIP       0
+#define TSL_RESTORE_OVERWRITE  1
+typedef struct {
+    int32_t rule;            /* TSL_EVICT_*                                               */
+    int32_t sid;             /* box rules: submap slot, -1 = every slot                   */
+    int32_t lo[3], hi[3];    /* box rules: inclusive voxel box                            */
+    int32_t release;         /* 1 = give the selected bricks back, 0 = snapshot           */
+    int32_t reserved_;
+} tsl_evict_cfg;
+typedef struct {
+    int32_t selected, missing, moved, bricks_before, bricks_after, restored, skipped, reserved_;
+} tsl_evict_stats;
+int  tsl_tsdf_evict(tsl_tsdf* m, const tsl_evict_cfg* cfg, const int32_t* keys_in, int64_t nkeys, int32_t* keys, uint32_t* tw, int8_t* obs, int8_t* occ,
+                    uint16_t* col, int64_t cap, tsl_evict_stats* stats);
+int  tsl_tsdf_evict_dev(tsl_tsdf* m, const tsl_evict_cfg* cfg, const void* keys_in_dev, int64_t nkeys, void* keys_dev, void* tw_dev, void* obs_dev,
+                        void* occ_dev, void* col_dev, int64_t cap, tsl_evict_stats* stats, void* user_stream);
+int  tsl_tsdf_restore_bricks(tsl_tsdf* m, const int32_t* keys, const uint32_t* tw, const int8_t* obs, const int8_t* occ, const uint16_t* col, int64_t n,
+                             int sid, int on_conflict, tsl_evict_stats* stats);
+int  tsl_tsdf_restore_bricks_dev(tsl_tsdf* m, const void* keys_dev, const void* tw_dev, const void* obs_dev, const void* occ_dev, const void* col_dev,
+                                 int64_t n, int sid, int on_conflict, tsl_evict_stats* stats, void* user_stream);
+int  tsl_tsdf_brick_keys(tsl_tsdf* m, int32_t* keys, int64_t cap, int32_t* n);
+int  tsl_tsdf_brick_keys_dev(tsl_tsdf* m, void* keys_dev, int64_t cap, int32_t* n, void* user_stream);
 
 /* ---- visualisation exports (device-resident result buffers, max_disp_particles rows) ---------- */
 /* cvt_TSDF_surface_to_voxels[_to]  dense_tsdf.py:323-365.  add_to_cur: keep the current count and

@@ -13,13 +13,14 @@ K_NAV_PROJECT, K_NAV_EDT, K_NAV_EDT_ROWS = 21, 22, 23
 K_NAV_FIELD_SEED, K_NAV_FIELD_ROUND, K_NAV_FIELD_PARENT, K_NAV_FIELD_PATHS = 24, 25, 26, 27
 K_NAV_TERRAIN_COLUMNS, K_NAV_TERRAIN_WINDOW = 28, 29
 K_ALIGN_RGBD = 30
+K_EVICT = 31
 KERNEL_NAMES = {K_VOXELIZE: "voxelize", K_SORT: "sort", K_RAYS: "build_rays", K_INTEGRATE: "integrate",
                 K_FINALIZE: "finalize", K_MESH: "marching_cubes", K_SEGMENTS: "segments", K_BIN: "bin", K_ESDF: "esdf", K_FUSE: "fuse", K_REGISTER: "register",
                 K_REGISTER_SCORE: "register_score", K_FRONTIER_MARK: "frontier_mark", K_FRONTIER_LABEL: "frontier_label", K_FRONTIER_JOIN: "frontier_join",
                 K_FRONTIER_SUM: "frontier_sum", K_FRONTIER_EMIT: "frontier_emit", K_VIEW_GAIN: "view_gain", K_ALIGN: "align", K_ALIGN_POINTS: "align_points",
                 K_PATH_SCORE: "path_score", K_NAV_PROJECT: "nav_project", K_NAV_EDT: "nav_edt", K_NAV_EDT_ROWS: "nav_edt_rows",
                 K_NAV_FIELD_SEED: "nav_field_seed", K_NAV_FIELD_ROUND: "nav_field_round", K_NAV_FIELD_PARENT: "nav_field_parent",
-                K_NAV_FIELD_PATHS: "nav_field_paths", K_NAV_TERRAIN_COLUMNS: "nav_terrain_columns", K_NAV_TERRAIN_WINDOW: "nav_terrain_window", K_ALIGN_RGBD: "align_rgbd"}
+                K_NAV_FIELD_PATHS: "nav_field_paths", K_NAV_TERRAIN_COLUMNS: "nav_terrain_columns", K_NAV_TERRAIN_WINDOW: "nav_terrain_window", K_ALIGN_RGBD: "align_rgbd", K_EVICT: "evict"}
 
 
 class TsdfCfg(C.Structure):
@@ -253,6 +254,23 @@ class NavTerrainCfg(C.Structure):
 TERRAIN_NO_HEIGHT, TERRAIN_NO_STAT, TERRAIN_NO_SLOPE = 32767, 65535, 0xffffffff
 
 
+EVICT_KEEP_BOX, EVICT_CLEAR_BOX, EVICT_KEYS = 0, 1, 2      # TSL_EVICT_*: the selection rules of DenseTSDF.evict
+RESTORE_SKIP, RESTORE_OVERWRITE = 0, 1                      # TSL_RESTORE_*
+
+
+class EvictCfg(C.Structure):
+    """tsl_evict_cfg (tsl_tsdf_evict): the rule, the slot of the box rules (-1 = every slot), the inclusive voxel box, release 1 = give the bricks back"""
+    _fields_ = [("rule", C.c_int32), ("sid", C.c_int32), ("lo", C.c_int32 * 3), ("hi", C.c_int32 * 3), ("release", C.c_int32), ("reserved_", C.c_int32)]
+
+
+class EvictStats(C.Structure):
+    """tsl_evict_stats"""
+    _fields_ = [(n, C.c_int32) for n in ("selected", "missing", "moved", "bricks_before", "bricks_after", "restored", "skipped", "reserved_")]
+
+    def as_dict(self):
+        return {n: int(getattr(self, n)) for n, _ in self._fields_ if n != "reserved_"}
+
+
 class TslError(RuntimeError):
     pass
 
@@ -295,6 +313,12 @@ SIGNATURES = {
     "tsl_tsdf_export_sparse": (C.c_int, [vp, vp, vp, vp, vp, vp, i64, pi64]),
     "tsl_tsdf_import_sparse": (C.c_int, [vp, C.c_int, vp, vp, vp, vp, vp, i64]),
     "tsl_tsdf_export_occupied": (C.c_int, [vp, vp, vp, i64, pi64]),
+    "tsl_tsdf_evict": (C.c_int, [vp, C.POINTER(EvictCfg), vp, i64, vp, vp, vp, vp, vp, i64, C.POINTER(EvictStats)]),
+    "tsl_tsdf_evict_dev": (C.c_int, [vp, C.POINTER(EvictCfg), vp, i64, vp, vp, vp, vp, vp, i64, C.POINTER(EvictStats), vp]),
+    "tsl_tsdf_restore_bricks": (C.c_int, [vp, vp, vp, vp, vp, vp, i64, C.c_int, C.c_int, C.POINTER(EvictStats)]),
+    "tsl_tsdf_restore_bricks_dev": (C.c_int, [vp, vp, vp, vp, vp, vp, i64, C.c_int, C.c_int, C.POINTER(EvictStats), vp]),
+    "tsl_tsdf_brick_keys": (C.c_int, [vp, vp, i64, pi32]),
+    "tsl_tsdf_brick_keys_dev": (C.c_int, [vp, vp, i64, pi32, vp]),
     "tsl_tsdf_surface_voxels": (C.c_int, [vp, vp, C.c_int, pi32]),
     "tsl_tsdf_slice_voxels": (C.c_int, [vp, f32, f32, C.c_int, pi32]),
     "tsl_tsdf_read_exports": (C.c_int, [vp, vp, vp, vp, i64]),

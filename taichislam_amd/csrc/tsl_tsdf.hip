@@ -1154,6 +1154,7 @@ void tsl_tsdf_destroy(tsl_tsdf* m)
     nav_terrain_release(m);
     nav_field3_release(m);
     nav_corridor_release(m);
+    evict_release(m);
     topo_map_gone(m);
     void* ptrs[] = { m->M.table, m->M.tw, m->M.obs, m->M.occ, m->M.col, m->M.owner, m->M.pool_top, m->F.slot_tab, m->F.touched, m->F.touched_b, m->F.acc, m->F.accw, m->F.dbg,
                      m->exp_xyz, m->exp_rgb, m->exp_val, m->num_particles, m->colormap, m->pose_dev, m->xbuf,

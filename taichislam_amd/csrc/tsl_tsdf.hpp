@@ -235,6 +235,8 @@ void nav_terrain_release(tsl_tsdf* m);
 void nav_field3_release(tsl_tsdf* m);    // tsl_nav_field3.hip: the 3-D solver's instance
 struct NavCorridorState;                 // tsl_nav_corridor.hip: the bit volume and the per-cell boxes of the corridors (allocated by the first call)
 void nav_corridor_release(tsl_tsdf* m);
+struct EvictState;                       // tsl_evict.hip: scratch of evict / restore (allocated by the first call)
+void evict_release(tsl_tsdf* m);
 void topo_map_gone(tsl_tsdf* m);         // tsl_topo.hip: the topology graphs bound to this map refuse every call from now on
 }  // namespace tsl
 
@@ -313,6 +315,7 @@ struct tsl_tsdf {
     tsl::NavTerrainState* nav_terrain;   // tsl_nav_terrain.hip (allocated by the first call)
     tsl::NavFieldState* nav_field3;      // tsl_nav_field3.hip (allocated by the first call)
     tsl::NavCorridorState* nav_corridor; // tsl_nav_corridor.hip (allocated by the first call)
+    tsl::EvictState* evict;              // tsl_evict.hip (allocated by the first call)
 };
 
 namespace tsl {

@@ -52,7 +52,7 @@ class _Device:
     def __init__(self, dev):
         torch = _torch()
         if _Device._kinds is None:
-            _Device._kinds = device_dtypes(torch)
+            _Device._kinds = dict(device_dtypes(torch), i1=torch.int8)      # (int8: the obs / occ planes of evict and restore_bricks)
         self.dev, self._empty, self._zeros, self._stream = dev, torch.empty, torch.zeros, torch.cuda.current_stream
 
     @staticmethod
