@@ -1061,6 +1061,56 @@ int  tsl_topo_buffers_dev(tsl_topo* t, void** tri_vertices_dev, void** normal_de
 int  tsl_topo_read_facelets(tsl_topo* t, int64_t first, int64_t n, float* tri_vertices, float* v0, float* edge1, float* edge2, float* normal, float* centre,
                             int32_t* poly);
 
+/* ---- depth conditioning (tsl_depth.hip): a batch of uint16 millimetre frames, as the sensor delivers them, loses its flying pixels
+ * and speckle, has the pixels it keeps smoothed by an integer bilateral filter, and is halved into up to three coarser levels -- one launch for the batch
+ * and one per level.  Every integrating and tracking entry point takes raw depth at face value; this pass is what a caller with a real camera puts in
+ * front of them.  The handle is its own type: it owns the tables and knows no map, touches none and issues nobody's queued frames.  Everything is integer, so
+ * the answer depends on no schedule; tests/depth_condition_ref.py restates it byte for byte.
+ *
+ * DEFINITION.  depth u16 [n][h][w] in millimetres, 1 <= n <= 64, 1 <= h, w <= 8192, n h w <= 2^28.
+ *   Tables (tsl_depth_set_tables): tol u16 [256], every entry in 1 .. 32767: the tolerance of a pixel of depth d is t(d) = tol[d >> 8] mm; ws u8 [5][5], the
+ *     spatial weight by (|dy|, |dx|); wr u8 [17], the range weight by q; ws[0][0] * wr[0] > 0.  The library derives rq[b] = min(65535, (16 << 16) / tol[b]).
+ *   Status, exactly one per pixel, the rules tested in this order; a pixel outside the image never counts as anything:
+ *     1 HOLE    d == 0
+ *     2 RANGE   d < d_min_mm or d > d_max_mm.  A pixel that is neither HOLE nor RANGE is a CANDIDATE.
+ *     3 SPARSE  fewer than min_support of the 8 neighbours are candidates q with |d_q - d| <= t(d) (the centre's tolerance)
+ *     4 EDGE    a seed lies within Chebyshev distance `erode`.  Seeds: the SPARSE pixels, and the HOLE pixels when flags bit 0 is set.  RANGE pixels and the
+ *               image border are no seeds.
+ *     0 KEPT    everything else
+ *   Output: a pixel that is not KEPT gives 0.  For a KEPT pixel p the members are the KEPT pixels q of the (2 radius + 1)^2 window with a = |d_q - d_p| <=
+ *     t(d_p); qi = (a * rq[d_p >> 8]) >> 16 (at most 16; the product fits 32 bits); wgt = ws[|dy|][|dx|] * wr[qi]; num = sum wgt * (d_q - d_p), den = sum wgt
+ *     (> 0: the centre is a member); off = floor((2 num + den) / (2 den)); out = clamp(d_p + off, 1, 65535).  radius 0: out = d_p.
+ *   counts int64 [n][5]: the pixels per status and frame; zeroed by the call.
+ *   Levels: level 0 is the output; level l + 1 has h' = h / 2, w' = w / 2 (an odd last row or column is dropped).  Of the four source pixels the non-zero
+ *     ones are valid; fewer than min_valid of them give 0; otherwise ref = the smallest valid depth (the foreground wins), the members are the valid pixels
+ *     with d - ref <= t(ref), m their number, out = floor((2 * sum of the members + m) / (2 m)).
+ * cfg: n, h, w; d_min_mm <= d_max_mm; min_support 0 .. 8; erode 0 .. 3; radius 0 .. 4; flags bit 0 = holes are seeds; levels 0 .. 3; min_valid 1 .. 4.
+ * tsl_depth_condition takes HOST pointers: it stages, runs on a stream of the handle and waits.  status, counts and the level pointers may be NULL; a level
+ *   above cfg->levels is ignored; a level left out below one that is given is computed in a buffer of the handle.
+ * tsl_depth_condition_dev takes DEVICE pointers and runs on `user_stream` itself, asynchronously: the result is ordered with whatever the caller queues there
+ *   next, an integration of `out` included.  One handle serves one stream at a time.  depth, out and the levels must be 2-byte aligned, counts 8-byte.
+ * Output and input must not overlap (equal pointers are refused).
+ * TSL_ERR_ARG (the text names the entry point), before anything is launched or written: a null handle, cfg, depth or out; tables not set or out of range; a
+ * configuration outside the ranges above; a level asked for that has no pixels (h >> levels or w >> levels is 0); an output that overlaps the input. */
+typedef struct tsl_depth tsl_depth;
+typedef struct {
+    int32_t n, h, w;
+    int32_t d_min_mm, d_max_mm, min_support, erode, radius, flags, levels, min_valid, reserved_;
+} tsl_depth_cfg;
+#define TSL_DEPTH_KEPT 0
+#define TSL_DEPTH_HOLE 1
+#define TSL_DEPTH_RANGE 2
+#define TSL_DEPTH_SPARSE 3
+#define TSL_DEPTH_EDGE 4
+int  tsl_depth_create(int device, tsl_depth** out);
+void tsl_depth_destroy(tsl_depth* t);
+/* copies the tables to the device and waits; TSL_ERR_ARG and nothing changed when an entry is out of range */
+int  tsl_depth_set_tables(tsl_depth* t, const uint16_t* tol /* [256] */, const uint8_t* ws /* [5][5] */, const uint8_t* wr /* [17] */);
+int  tsl_depth_condition(tsl_depth* t, const tsl_depth_cfg* cfg, const uint16_t* depth, uint16_t* out, uint8_t* status, int64_t* counts, uint16_t* lvl1,
+                         uint16_t* lvl2, uint16_t* lvl3);
+int  tsl_depth_condition_dev(tsl_depth* t, const tsl_depth_cfg* cfg, const void* depth_dev, void* out_dev, void* status_dev, void* counts_dev, void* lvl1_dev,
+                             void* lvl2_dev, void* lvl3_dev, void* user_stream);
+
 /* ---- terrain layers for ground robots (tsl_nav_terrain.hip): per height band and (x, y) column the height of the surface a robot
  * can stand on, over the robot's footprint the step and the slope of that surface, and a class, a distance and a cost in the vocabulary of
  * tsl_tsdf_nav_grid, so that tsl_tsdf_nav_field and the OccupancyGrid adapters take them unchanged.  Where nav_grid calls a column an obstacle as soon as

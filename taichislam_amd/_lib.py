@@ -271,6 +271,15 @@ class EvictStats(C.Structure):
         return {n: int(getattr(self, n)) for n, _ in self._fields_ if n != "reserved_"}
 
 
+class DepthCfg(C.Structure):
+    """tsl_depth_cfg (tsl_depth_condition): the batch n x h x w, the range gate in mm, min_support 0 .. 8, erode 0 .. 3, radius 0 .. 4, flags bit 0 = holes
+    erode too, levels 0 .. 3, min_valid 1 .. 4"""
+    _fields_ = [(n, C.c_int32) for n in ("n", "h", "w", "d_min_mm", "d_max_mm", "min_support", "erode", "radius", "flags", "levels", "min_valid", "reserved_")]
+
+
+DEPTH_KEPT, DEPTH_HOLE, DEPTH_RANGE, DEPTH_SPARSE, DEPTH_EDGE = range(5)      # TSL_DEPTH_*: the status codes of DepthConditioner.condition
+
+
 class TslError(RuntimeError):
     pass
 
@@ -422,6 +431,11 @@ SIGNATURES = {
     "tsl_topo_add_poly": (C.c_int, [vp, vp, i32, vp, f32, vp, vp, vp, vp, pi32]),
     "tsl_topo_buffers_dev": (C.c_int, [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), pi64, pi32]),
     "tsl_topo_read_facelets": (C.c_int, [vp, i64, i64, vp, vp, vp, vp, vp, vp, vp]),
+    "tsl_depth_create": (C.c_int, [C.c_int, C.POINTER(vp)]),
+    "tsl_depth_destroy": (None, [vp]),
+    "tsl_depth_set_tables": (C.c_int, [vp, vp, vp, vp]),
+    "tsl_depth_condition": (C.c_int, [vp, C.POINTER(DepthCfg), vp, vp, vp, vp, vp, vp, vp]),
+    "tsl_depth_condition_dev": (C.c_int, [vp, C.POINTER(DepthCfg), vp, vp, vp, vp, vp, vp, vp, vp]),
     "tsl_tsdf_set_option": (C.c_int, [vp, C.c_char_p, C.c_int]),
     "tsl_tsdf_get_option": (C.c_int, [vp, C.c_char_p, C.POINTER(C.c_int)]),
     "tsl_tsdf_prof_enable": (C.c_int, [vp, C.c_int]),

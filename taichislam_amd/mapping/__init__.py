@@ -5,3 +5,4 @@ from .taichi_octomap import Octomap  # noqa: F401
 from .marching_cube_mesher import MarchingCubeMesher  # noqa: F401
 from .submap_mapping import SubmapMapping  # noqa: F401
 from .topo_graph import TopoGraphGen  # noqa: F401
+from .depth_conditioner import DepthConditioner  # noqa: F401
