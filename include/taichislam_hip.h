@@ -1111,6 +1111,76 @@ int  tsl_depth_condition(tsl_depth* t, const tsl_depth_cfg* cfg, const uint16_t*
 int  tsl_depth_condition_dev(tsl_depth* t, const tsl_depth_cfg* cfg, const void* depth_dev, void* out_dev, void* status_dev, void* counts_dev, void* lvl1_dev,
                              void* lvl2_dev, void* lvl3_dev, void* user_stream);
 
+/* ---- pose graph (tsl_pose_graph.hip): the poses of submaps under relative-pose constraints, solved once per VARIANT in one launch.
+ * A variant is a bit mask over the edges (bit e & 63 of word e >> 6: edge e takes part); one workgroup of 256 threads runs the whole Levenberg-Marquardt
+ * loop of one variant in float64, with no atomic and no library call on the device.  Every sum below has a fixed order, so a result is one defined answer:
+ * tests/pose_graph_ref.py restates this text in numpy and the tests compare bit for bit.  The handle needs no map.
+ *   Conventions.  A pose P_i = (R_i, T_i) takes submap coordinates to the common frame (what tsl_tsdf_set_base_pose_submap takes).  An edge (a, b, Z = (Rz,
+ *   Tz), L) says that P_b^-1 P_a was measured as Z -- what tsl_tsdf_register_submap returns for source a and destination b -- with the information matrix L
+ *   in twist order (v, omega), the left twist in b's frame.  A twist xi = (v, omega) acts as tsl_pose_retract does (the Cayley map): R <- C R, T <- C T + v.
+ *   "dot3" and "dot6" below are sums of products added left to right: (a0 b0 + a1 b1) + a2 b2, and so on to six terms.
+ *   Residual of an edge: Rx = R_b^T R_a, Tx = R_b^T (T_a - T_b), R_D = Rx Rz^T, T_D = Tx - R_D Tz (every entry a dot3 over the summed index 0, 1, 2),
+ *   den = 1 + ((R_D00 + R_D11) + R_D22), r = (T_D, (2 * vee(R_D - R_D^T)) / den) with vee = (R_D21 - R_D12, R_D02 - R_D20, R_D10 - R_D01): the twist whose
+ *   retraction from the identity is the error D.  An edge with den < 1 (a rotation error above 120 degrees) is FLIPPED.
+ *   Cost of an edge: c = dot6(r, L r), each row of L r a dot6.  chi = sqrt(c); with huber > 0 and chi > huber the weight is wgt = huber / chi and the edge
+ *   counts (2 huber) chi - huber huber in the cost, otherwise wgt = 1 and it counts c.  Lw = wgt * L entry by entry.
+ *   Linearisation, every pose moved by a left twist in the common frame: with Ri = R_b^T and ti = -(R_b^T T_b), A d = (Ri v + ti x (Ri w), Ri w) for d = (v,
+ *   w) and A^T m = (R_b m_v, R_b (m_w - ti x m_v)); dr/dxi_a = A, dr/dxi_b = -A, the Jacobian of the inverse retraction taken as the identity.  Per edge
+ *   q_e = A^T (Lw r) and W_e = A^T Lw A, column j of it being A^T (Lw (A e_j)).  Per pose Hd_i = the sum of W_e (its upper triangle, the 21 numbers in the
+ *   order of tsl_align_sums.H) and g_i = the sum of +q_e where the pose is a, -q_e where it is b, over its enabled incident edges IN ASCENDING EDGE INDEX
+ *   from 0.  Rows of fixed poses are 0.
+ *   Operator, for one 6-vector p_i per pose (0 for fixed poses): per enabled edge u_e = A^T (Lw (A (p_a - p_b))); per free pose y_i = (damping * Hd_i[k][k])
+ *   * p_i[k], then + u_e / - u_e over the incident edges in ascending index.  Preconditioner: per free pose the Cholesky factor of Hd_i with its diagonal
+ *   multiplied by (1 + damping) as tsl_align_solve does (H_kk + damping * H_kk), eliminated in tsl_align_solve's order; a pivot <= 0 or not finite is singular.
+ *   Reductions: a sum over poses (or edges) is taken in 256 classes: class c adds the terms of i = c, c + 256, ... in ascending order from 0.0, then
+ *   s[c] += s[c + h] for h = 128, 64, .., 1 and s[0] is the sum.  The order depends on N and E only.
+ *   Linear solve, H x = -g by preconditioned conjugate gradients: x = 0, r = -g, z = M^-1 r, p = z, rz = rz0 = sum dot6(r_i, z_i).  While fewer than pcg_max
+ *   iterations are done and not rz <= (pcg_tol * pcg_tol) * rz0: y = operator(p), pAp = sum dot6(p_i, y_i), stop unless pAp > 0, alpha = rz / pAp,
+ *   x += alpha p, r -= alpha y, z = M^-1 r, rz' = sum dot6(r_i, z_i), beta = rz' / rz, p = z + beta p, rz = rz'.
+ *   Outer loop, at most cfg.iters (<= 64) iterations: evaluate the edges at the current poses (cost = the sum over the enabled edges), gather and factor
+ *   (singular: status 3, the iteration is recorded with cost_after = cost_before), solve, retract every free pose by its x_i into trial poses, evaluate them.
+ *   max_step = sqrt(max dot6(x_i, x_i)).  The trial is REJECTED when an enabled edge is flipped there, its cost is not finite or not below the current cost:
+ *   damping *= damping_up, status 2 once damping > damping_max.  Otherwise it is ACCEPTED: damping = max(damping / damping_down, damping_min), status 0 when
+ *   max_step < min_step or cost - trial <= rel_tol * cost.  Status 1: the iterations ran out.  Status 4, decided on the host by a union-find per variant
+ *   before the launch: some connected component of the enabled edges holds a free pose and no fixed one (a free pose without an enabled edge included);
+ *   status 5: an enabled edge is flipped at the given poses.  Variants of status 4 and 5 are not solved and return the poses as given.
+ *   Outputs per variant: the poses, for EVERY edge (enabled or not) r and c = r^T L r at the final poses -- the value of a disabled edge under the solution
+ *   that did not see it is what a leave-one-out check reads: a raw cost to compare and rank, not a chi-square to threshold -- and a tsl_pgo_report with the
+ *   final cost, the status, the iteration count and a record per iteration (the rest zero).
+ * Capacities: max_poses <= 8192, max_edges <= 131072, max_variants <= 1024 and max_variants * (720 * max_poses + 56 * max_edges) bytes of workspace plus the
+ * tables under 1 GiB (720 = the trial pose, Hd, the factor and six 6-vectors per pose; 56 = u_e and wgt per edge): 4096 poses, 32768 edges, 1 variant and 1024
+ * poses, 8192 edges, 256 variants both fit.  The search direction p lives in LDS up to 1024 poses and in the workspace above; the results do not differ.
+ * Arguments: R f64 [N][9] row-major, T f64 [N][3], fixed u8 [N] (linearize: may be NULL), ij i32 [E][2] = (a, b), Z f64 [E][12] = Rz row-major then Tz,
+ * L f64 [E][21], masks u64 [B][ceil(E / 64)] (NULL: one variant, every edge on; B is then ignored).  Duplicate edges between one pair simply add.
+ * TSL_ERR_ARG (the text names the entry point): a null pointer, N, E or B outside 1 .. the capacity, a == b or an index outside the poses, no fixed pose
+ * (solve), a cfg value that is negative or not finite, iters > 64, pcg_max > 100000, damping_down = 0, and in the host forms a number that is not finite or a
+ * negative diagonal of L.  The host forms copy, run and wait.  The _dev forms take R, T, Z, L and the outputs as DEVICE pointers and run asynchronously on the
+ * handle's stream behind the work queued on `user_stream`, which then waits for them; ij, fixed and the masks stay HOST pointers in both forms, because the
+ * incidence lists and the status-4 check are made on the host (they are copied before the call returns).  The _dev forms cannot check the values on the device. */
+typedef struct tsl_pgo tsl_pgo;
+typedef struct {
+    int32_t iters, pcg_max;
+    double  damping, damping_up, damping_down, damping_min, damping_max, pcg_tol, min_step, rel_tol, huber;
+} tsl_pgo_cfg;
+typedef struct { double cost_before, cost_after, max_step, damping; int32_t pcg_iters, accepted; } tsl_pgo_iter;      /* 40 bytes */
+typedef struct { int32_t status, iterations; double cost; tsl_pgo_iter it[64]; } tsl_pgo_report;                       /* 2576 bytes */
+
+int  tsl_pgo_create(int device, int32_t max_poses, int32_t max_edges, int32_t max_variants, tsl_pgo** out);
+void tsl_pgo_destroy(tsl_pgo* h);
+/* one mask (NULL: every edge on): per edge r f64 [E][6], cost f64 [E] = r^T L r, flipped u8 [E]; per pose Hd f64 [N][21] and g f64 [N][6].  For a caller
+ * with a solver of its own. */
+int  tsl_pgo_linearize(tsl_pgo* h, int32_t N, const double* R, const double* T, const uint8_t* fixed, int32_t E, const int32_t* ij, const double* Z,
+                       const double* L, const uint64_t* mask, double huber, double* r, double* cost, uint8_t* flipped, double* Hd, double* g);
+int  tsl_pgo_linearize_dev(tsl_pgo* h, int32_t N, const void* R_dev, const void* T_dev, const uint8_t* fixed, int32_t E, const int32_t* ij, const void* Z_dev,
+                           const void* L_dev, const uint64_t* mask, double huber, void* r_dev, void* cost_dev, void* flipped_dev, void* Hd_dev, void* g_dev,
+                           void* user_stream);
+/* outputs: R_out f64 [B][N][9], T_out f64 [B][N][3], r f64 [B][E][6], cost f64 [B][E], reports [B] */
+int  tsl_pgo_solve(tsl_pgo* h, int32_t N, const double* R, const double* T, const uint8_t* fixed, int32_t E, const int32_t* ij, const double* Z, const double* L,
+                   int32_t B, const uint64_t* masks, const tsl_pgo_cfg* cfg, double* R_out, double* T_out, double* r, double* cost, tsl_pgo_report* reports);
+int  tsl_pgo_solve_dev(tsl_pgo* h, int32_t N, const void* R_dev, const void* T_dev, const uint8_t* fixed, int32_t E, const int32_t* ij, const void* Z_dev,
+                       const void* L_dev, int32_t B, const uint64_t* masks, const tsl_pgo_cfg* cfg, void* R_out_dev, void* T_out_dev, void* r_dev, void* cost_dev,
+                       void* reports_dev, void* user_stream);
+
 /* ---- terrain layers for ground robots (tsl_nav_terrain.hip): per height band and (x, y) column the height of the surface a robot
  * can stand on, over the robot's footprint the step and the slope of that surface, and a class, a distance and a cost in the vocabulary of
  * tsl_tsdf_nav_grid, so that tsl_tsdf_nav_field and the OccupancyGrid adapters take them unchanged.  Where nav_grid calls a column an obstacle as soon as

@@ -280,6 +280,18 @@ class DepthCfg(C.Structure):
 DEPTH_KEPT, DEPTH_HOLE, DEPTH_RANGE, DEPTH_SPARSE, DEPTH_EDGE = range(5)      # TSL_DEPTH_*: the status codes of DepthConditioner.condition
 
 
+class PgoCfg(C.Structure):
+    """tsl_pgo_cfg (tsl_pgo_solve): iters 0 .. 64, pcg_max 0 .. 100000, huber 0 = off"""
+    _fields_ = [("iters", C.c_int32), ("pcg_max", C.c_int32)] + [(n, C.c_double) for n in ("damping", "damping_up", "damping_down", "damping_min", "damping_max",
+                                                                                             "pcg_tol", "min_step", "rel_tol", "huber")]
+
+
+PGO_STATUS = ("converged", "iterations", "stalled", "singular", "unanchored", "flipped")      # tsl_pgo_report.status
+# tsl_pgo_report as a numpy record: 2576 bytes per variant
+PGO_ITER_FIELDS = [("cost_before", "<f8"), ("cost_after", "<f8"), ("max_step", "<f8"), ("damping", "<f8"), ("pcg_iters", "<i4"), ("accepted", "<i4")]
+PGO_REPORT_FIELDS = [("status", "<i4"), ("iterations", "<i4"), ("cost", "<f8"), ("it", PGO_ITER_FIELDS, (64,))]
+
+
 class TslError(RuntimeError):
     pass
 
@@ -436,6 +448,12 @@ SIGNATURES = {
     "tsl_depth_set_tables": (C.c_int, [vp, vp, vp, vp]),
     "tsl_depth_condition": (C.c_int, [vp, C.POINTER(DepthCfg), vp, vp, vp, vp, vp, vp, vp]),
     "tsl_depth_condition_dev": (C.c_int, [vp, C.POINTER(DepthCfg), vp, vp, vp, vp, vp, vp, vp, vp]),
+    "tsl_pgo_create": (C.c_int, [C.c_int, i32, i32, i32, C.POINTER(vp)]),
+    "tsl_pgo_destroy": (None, [vp]),
+    "tsl_pgo_linearize": (C.c_int, [vp, i32, vp, vp, vp, i32, vp, vp, vp, vp, C.c_double, vp, vp, vp, vp, vp]),
+    "tsl_pgo_linearize_dev": (C.c_int, [vp, i32, vp, vp, vp, i32, vp, vp, vp, vp, C.c_double, vp, vp, vp, vp, vp, vp]),
+    "tsl_pgo_solve": (C.c_int, [vp, i32, vp, vp, vp, i32, vp, vp, vp, i32, vp, C.POINTER(PgoCfg), vp, vp, vp, vp, vp]),
+    "tsl_pgo_solve_dev": (C.c_int, [vp, i32, vp, vp, vp, i32, vp, vp, vp, i32, vp, C.POINTER(PgoCfg), vp, vp, vp, vp, vp, vp]),
     "tsl_tsdf_set_option": (C.c_int, [vp, C.c_char_p, C.c_int]),
     "tsl_tsdf_get_option": (C.c_int, [vp, C.c_char_p, C.POINTER(C.c_int)]),
     "tsl_tsdf_prof_enable": (C.c_int, [vp, C.c_int]),

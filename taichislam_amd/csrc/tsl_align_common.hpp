@@ -160,11 +160,10 @@ static void al_system(const tsl_align_sums* s, double damping, double Hm[6][6], 
     for (int a = 0; a < 6; ++a) { b[a] = (double)s->b[a] * (1.0 / 1048576.0); Hm[a][a] += damping * Hm[a][a]; }
 }
 
-// xi = -H^-1 b of a ready system by Cholesky L L^T without pivoting, column by column; false (xi = 0) when a pivot is <= 0 or not finite
-static bool al_solve_system(const double Hm[6][6], const double b[6], double xi[6])
+// Hm = L L^T by Cholesky without pivoting, column by column (only the lower triangle of Lm is written); false when a pivot is <= 0 or not finite.
+// Host and device: the pose graph (tsl_pose_graph.hip) factors its 6 x 6 blocks with the elimination order of the trackers.
+__host__ __device__ static inline bool al_cholesky(const double Hm[6][6], double Lm[6][6])
 {
-    double Lm[6][6], y[6];
-    for (int a = 0; a < 6; ++a) xi[a] = 0.0;
     for (int j = 0; j < 6; ++j) {
         double d = Hm[j][j];
         for (int k = 0; k < j; ++k) d -= Lm[j][k] * Lm[j][k];
@@ -176,17 +175,32 @@ static bool al_solve_system(const double Hm[6][6], const double b[6], double xi[
             Lm[i][j] = t / Lm[j][j];
         }
     }
-    for (int i = 0; i < 6; ++i) {                                  // L y = -b
-        double t = -b[i];
+    return true;
+}
+
+// x = (L L^T)^-1 c: L y = c forwards, L^T x = y backwards
+__host__ __device__ static inline void al_cholesky_solve(const double Lm[6][6], const double c[6], double x[6])
+{
+    double y[6];
+    for (int i = 0; i < 6; ++i) {
+        double t = c[i];
         for (int k = 0; k < i; ++k) t -= Lm[i][k] * y[k];
         y[i] = t / Lm[i][i];
     }
-    double x[6];
-    for (int i = 5; i >= 0; --i) {                                 // L^T x = y
+    for (int i = 5; i >= 0; --i) {
         double t = y[i];
         for (int k = i + 1; k < 6; ++k) t -= Lm[k][i] * x[k];
         x[i] = t / Lm[i][i];
     }
+}
+
+// xi = -H^-1 b of a ready system; false (xi = 0) when a pivot is <= 0 or not finite
+static bool al_solve_system(const double Hm[6][6], const double b[6], double xi[6])
+{
+    double Lm[6][6], nb[6], x[6];
+    for (int a = 0; a < 6; ++a) { xi[a] = 0.0; nb[a] = -b[a]; }
+    if (!al_cholesky(Hm, Lm)) return false;
+    al_cholesky_solve(Lm, nb, x);
     for (int a = 0; a < 6; ++a) if (!std::isfinite(x[a])) return false;
     for (int a = 0; a < 6; ++a) xi[a] = x[a];
     return true;
@@ -215,8 +229,8 @@ static bool al_solve_rgbd(const tsl_align_rgbd_sums* s, double lambda, double da
 static int64_t al_used(const tsl_align_sums& s) { return s.n_used; }
 static int64_t al_used(const tsl_align_rgbd_sums& s) { return s.geo.n_used; }                 // colour alone does not fix depth
 
-// the Cayley map of omega = xi[3..5]: R <- C R, T <- C T + v
-static void al_retract(const double xi[6], double R[9], double T[3])
+// the Cayley map of omega = xi[3..5]: R <- C R, T <- C T + v (host and device: the pose graph retracts its poses with it)
+__host__ __device__ static inline void al_retract(const double xi[6], double R[9], double T[3])
 {
     const double a[3] = { xi[3] * 0.5, xi[4] * 0.5, xi[5] * 0.5 };
     const double aa = (a[0] * a[0] + a[1] * a[1]) + a[2] * a[2], den = 1.0 + aa;

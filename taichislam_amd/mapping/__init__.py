@@ -6,3 +6,4 @@ from .marching_cube_mesher import MarchingCubeMesher  # noqa: F401
 from .submap_mapping import SubmapMapping  # noqa: F401
 from .topo_graph import TopoGraphGen  # noqa: F401
 from .depth_conditioner import DepthConditioner  # noqa: F401
+from .pose_graph import PoseGraph  # noqa: F401

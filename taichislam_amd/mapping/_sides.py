@@ -52,7 +52,8 @@ class _Device:
     def __init__(self, dev):
         torch = _torch()
         if _Device._kinds is None:
-            _Device._kinds = dict(device_dtypes(torch), i1=torch.int8)      # (int8: the obs / occ planes of evict and restore_bricks)
+            # (int8: the obs / occ planes of evict and restore_bricks; float64: the poses and residuals of the pose graph)
+            _Device._kinds = dict(device_dtypes(torch), i1=torch.int8, f8=torch.float64)
         self.dev, self._empty, self._zeros, self._stream = dev, torch.empty, torch.zeros, torch.cuda.current_stream
 
     @staticmethod

@@ -66,6 +66,9 @@ class SubmapMapping:
         self.map_send_handle = lambda buf: None
         self.traj_send_handle = lambda buf: None
         self._anchor = _Anchor()
+        self.opened = {}                          # frame id of an own submap -> the pose (R, T) it was opened at: the odometry edges of optimize_poses
+        self.constraints = []                     # add_constraint: (frame_a, frame_b, R, T, information)
+        self._pose_graph = None
         self.submap_collection = submap_type(**self.sub_opts)
         self.global_map = self.create_globalmap(global_opts)
         self.enable_texture = self.global_map.enable_texture
@@ -149,6 +152,88 @@ class SubmapMapping:
         info["guess"], info["submaps"] = (R0, T0), (sa, sb)
         return R, T, info
 
+    def add_constraint(self, frame_a, frame_b, R, T, information):
+        """Append a pose-graph constraint: P_b^-1 P_a was measured as (R, T) with the 6 x 6 information matrix `information` (twist order (v, omega), the left
+        twist in b's frame) -- exactly what register_submaps(frame_a, frame_b) / search_submaps return as R, T and info["information"].  Returns its index
+        in self.constraints."""
+        R, T, L = np.array(R, np.float64).reshape(3, 3), np.array(T, np.float64).reshape(3), np.array(information, np.float64).reshape(6, 6)
+        if frame_a == frame_b:
+            raise ValueError("add_constraint: a constraint joins two different submaps")
+        self.constraints.append((frame_a, frame_b, R, T, L))
+        return len(self.constraints) - 1
+
+    def _graph(self, odom_information, fixed):
+        """The pose graph as arrays.  Nodes: the known submaps in ascending frame id, at the global map's base poses.  Edges: first an odometry edge between
+        every two consecutive own submaps, measured from the poses they were opened at (a = the later one), then the constraints in the order they were
+        added.  fixed: frame ids, None = the first own submap."""
+        from ..utils.pose import pose_information
+        frames = sorted(self.submaps)
+        at = {f: n for n, f in enumerate(frames)}
+        g = self.global_map
+        sid = [self.submaps[f] for f in frames]
+        R, T = np.array(g.submaps_base_R_np[sid], np.float64), np.array(g.submaps_base_T_np[sid], np.float64)
+        own = sorted(f for f in self.opened if f in at)
+        if fixed is None:
+            if not own:
+                raise ValueError("optimize_poses: no own submap to fix; name the fixed frames")
+            fixed = [own[0]]
+        fx = np.zeros(len(frames), np.uint8)
+        fx[[at[f] for f in fixed]] = 1
+        Lo = pose_information(0.05, 0.02) if odom_information is None else np.array(odom_information, np.float64).reshape(6, 6)
+        ij, Rz, Tz, L = [], [], [], []
+        for prev, nxt in zip(own[:-1], own[1:]):
+            (Rp, Tp), (Rn, Tn) = self.opened[prev], self.opened[nxt]
+            ij.append((at[nxt], at[prev])); Rz.append(Rp.T @ Rn); Tz.append(Rp.T @ (Tn - Tp)); L.append(Lo)
+        n_odom = len(ij)
+        for fa, fb, Rc, Tc, Lc in self.constraints:
+            if fa not in at or fb not in at:
+                raise KeyError(f"a constraint names frame {fa if fa not in at else fb}, which opens no known submap")
+            ij.append((at[fa], at[fb])); Rz.append(Rc); Tz.append(Tc); L.append(Lc)
+        if not ij:
+            raise ValueError("optimize_poses: the graph has no edge")
+        return frames, R, T, fx, np.array(ij, np.int32), np.array(Rz), np.array(Tz), np.array(L), n_odom
+
+    def _solver(self, n, e, b):
+        """a PoseGraph with room for n poses, e edges and b variants on the global map's device, kept and regrown by doubling"""
+        from .pose_graph import PoseGraph
+        pg = self._pose_graph
+        if pg is None or pg.max_poses < n or pg.max_edges < e or pg.max_variants < b:
+            def cap(x, lo):
+                return max(lo, 1 << (int(x) - 1).bit_length())
+            self._pose_graph = pg = PoseGraph(cap(n, 64), cap(e, 256), cap(b, 1), device=getattr(self.global_map, "device", 0))
+        return pg
+
+    def optimize_poses(self, odom_information=None, fixed=None, apply=False, **solver_kw):
+        """Solve the pose graph of the known submaps (see _graph for its nodes and edges; odom_information: the 6 x 6 information of an odometry edge, None =
+        utils.pose_information(0.05, 0.02)).  Returns ({frame_id: (R, T)}, report): the optimised base poses and {"status" (PoseGraph.STATUS_NAMES index),
+        "iterations", "cost", "records", "edge_cost" (r^T L r per edge at the result), "edges" [(frame_a, frame_b)], "n_odometry"}.  apply=True passes the
+        poses to set_frame_poses; otherwise nothing moves.  solver_kw: the keywords of PoseGraph.solve."""
+        from .pose_graph import pack_measurements
+        frames, R, T, fx, ij, Rz, Tz, L, n_odom = self._graph(odom_information, fixed)
+        out = self._solver(len(frames), len(ij), 1).solve(R, T, fx, ij, pack_measurements(Rz, Tz), L, **solver_kw)
+        rep = out["report"][0]
+        poses = {f: (out["R"][0, n].copy(), out["T"][0, n].copy()) for n, f in enumerate(frames)}
+        report = {"status": int(rep["status"]), "iterations": int(rep["iterations"]), "cost": float(rep["cost"]), "records": rep["it"][:int(rep["iterations"])].copy(),
+                  "edge_cost": out["edge_cost"][0].copy(), "edges": [(frames[a], frames[b]) for a, b in ij], "n_odometry": n_odom}
+        if apply:
+            self.set_frame_poses(poses)
+        return poses, report
+
+    def check_constraints(self, odom_information=None, fixed=None, **solver_kw):
+        """Leave-one-out over the constraints, all in one launch: the graph is solved with every edge and once without each constraint, and constraint k is
+        read under the solution that did not see it.  Returns {"loo_cost" [K], "full_cost" [K], "status" [1 + K], "order": the constraints from the most
+        to the least consistent (ascending loo_cost)}.  The costs are raw r^T L r values to compare and rank: odometry drift loosens the prediction and L is
+        not its covariance, so they are no chi-square to threshold.  A constraint whose removal cuts the graph (status 4) reads inf.  Nothing moves."""
+        from .pose_graph import pack_measurements
+        if not self.constraints:
+            raise ValueError("check_constraints: no constraint")
+        frames, R, T, fx, ij, Rz, Tz, L, n_odom = self._graph(odom_information, fixed)
+        K = len(self.constraints)
+        out = self._solver(len(frames), len(ij), 1 + K).leave_one_out(R, T, fx, ij, pack_measurements(Rz, Tz), L, n_odom + np.arange(K), **solver_kw)
+        status = out["report"]["status"].astype(np.int32)
+        loo = np.where(status[1:] == 4, np.inf, out["loo_cost"])
+        return {"loo_cost": loo, "full_cost": out["full_cost"], "status": status, "order": np.argsort(loo, kind="stable")}
+
     # ---- submap life cycle -----------------------------------------------------------------------------------------------------------------
     def need_create_new_submap(self, is_keyframe, R=None, T=None):
         return self.frame_count == 0 or (bool(is_keyframe) and self.frame_count % self.keyframe_step == 0)
@@ -166,6 +251,7 @@ class SubmapMapping:
         for m in (self.global_map, col):
             m.set_base_pose_submap(sid, R, T)
         self.submaps[frame_id] = sid
+        self.opened[frame_id] = (np.array(R, np.float64), np.array(T, np.float64).reshape(3))
         self._anchor.pgo[frame_id] = (R, T)
         self.active_submap_frame_id = frame_id
         print(f"[SubmapMapping] frame {frame_id} opens submap {sid} ({sid + 1} local submaps)")
